@@ -7,7 +7,10 @@ in HBM before the timed region.  Instances are independent, so N GPUs run N cont
 collective (weak scaling); torch.distributed (RCCL) carries the barrier, the max-over-ranks time and a gathered
 per-rank timing vector.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline] [--no-secondary]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-secondary]]
+        A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds what takes work of its own: the measured
+        FP64 peaks, per-kernel times and roofline, the secondary figures (closed loops, latency, C5, strong scaling, PCIe) and the CPU baseline.
+        --dump-outputs DIR writes what the last timed step computed (the arrays a caller downloads) as DIR/<name>.npy, float64.
         --gpus N > 1 without WORLD_SIZE in the environment: bench.py re-launches itself as N ranks under
         `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` (what the driver does itself).
 Prints ONE JSON line on rank 0.
@@ -52,9 +55,12 @@ def parse_args(argv=None):
     ap.add_argument("--global-batch", type=int, default=0, help="STRONG scaling (SURVEY.md §8(d) C4 / BASELINE.json config 4): a fixed global batch, e.g. 8192, cut into "
                     "contiguous shards of global/G instances for G GPUs; overrides --batch")
     ap.add_argument("--n-intervals", type=int, default=100, help="horizon N (the metric is quoted at 100; other values are for tests)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: FP64 peaks, per-kernel times + roofline, the secondary "
+                    "figures and the CPU baseline (the --no-* switches below trim a --full run)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary figures (closed loops, latency, C5)")
     ap.add_argument("--no-plant-loop", action="store_true", help="skip only the closed-loop-around-the-plant figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (float64)")
     return ap.parse_args(argv)
 
 
@@ -105,6 +111,16 @@ class HipEngine:
         return dict(ok=bool((res["status"] >= 0).all() and (qps == 0).all()), out=out, n_intervals=n_intervals, ls_trials=int(res["ls_trials"]),
                     n_bad_mpc=int((res["status"] < 0).sum()), n_warn_mpc=int((res["status"] > 0).sum()), n_bad_wbc=int((qps != 0).any(axis=1).sum()))
 
+    def outputs(self):
+        """what a caller of the timed path receives after a step, instance-major: qmhip_mpc_download (node grid, primal solution x / u, per-instance perf
+        figures, status) and qmhip_wbc_download (the WBC output [v̇; contact forces; torques], QP status per level).  Node slots past num_nodes hold
+        nothing of this step and are written as zeros."""
+        import numpy as np
+        res = self.mpc.download(); out, qps = self.wbc.download(self.B)
+        live = np.arange(res["t"].shape[1])[None, :] < res["num_nodes"][:, None]
+        nodes = {k: np.where(live[:, :, None] if res[k].ndim == 3 else live, res[k], 0) for k in ("t", "event", "mode", "x", "u")}
+        return dict(num_nodes=res["num_nodes"], status=res["status"], perf=res["perf"], wbc_out=out, wbc_qp_status=qps), nodes
+
     def close(self):
         self.itf.close()
 
@@ -119,6 +135,25 @@ def timed_region(engine, steps, dist, device):
     engine.sync(); sharding.barrier(dist, device)
     mine = time.perf_counter() - t0
     return sharding.max_over_ranks(mine, dist, device), mine
+
+
+DUMP_BUDGET_BYTES = 48 << 20      # --dump-outputs writes at most this much (all ranks together)
+
+
+def dump_outputs(path, outs, rank, world):
+    """`outs` = (per-instance arrays, per-node arrays) of this rank's shard, written as float64 .npy files (prefixed rank<r>_ when there are several ranks).
+    The per-instance arrays are written whole; the per-node ones ([B][max_nodes](...)) for a fixed, seeded sample of instances when the whole would exceed
+    the budget, listed in node_sample_instances.npy."""
+    import numpy as np
+    small, nodes = ({k: np.asarray(v, dtype=np.float64) for k, v in d.items()} for d in outs)
+    B = len(small["status"])
+    room = DUMP_BUDGET_BYTES // world - sum(v.nbytes for v in small.values())
+    keep = int(room // max(1, sum(v.nbytes for v in nodes.values()) // B))
+    idx = np.arange(B) if keep >= B else np.sort(np.random.default_rng(1235).choice(B, keep, replace=False))
+    small.update({k: v[idx] for k, v in nodes.items()}); small["node_sample_instances"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in small.items():
+        np.save(os.path.join(path, ("" if world == 1 else "rank%d_" % rank) + k + ".npy"), v)
 
 
 def run(args, make_engine=HipEngine, backend="nccl", device="cuda"):
@@ -138,9 +173,10 @@ def run(args, make_engine=HipEngine, backend="nccl", device="cuda"):
     eng = make_engine(cfg, local)
     hip = getattr(eng, "name", "") == "hip"
     itf = eng.itf if hip else None
+    prof = hip and bool(getattr(args, "full", False))      # FP64 peaks, per-kernel times and the roofline: --full only (a plain run times the steps and nothing else)
 
     peak_mfma = peak_fma = None
-    if hip:
+    if prof:
         # roofline denominators measured on this very device before anything is timed ("microbenchmark it first"): FP64 matrix and
         # vector FMA throughput, ≈ 0.6 s of sustained FP64 work (which also brings a freshly booted device to its sustained clocks)
         peak_mfma = max(itf.microbench_fp64(True) for _ in range(12)); peak_fma = max(itf.microbench_fp64(False) for _ in range(6))
@@ -148,7 +184,7 @@ def run(args, make_engine=HipEngine, backend="nccl", device="cuda"):
         eng.step()
     eng.sync()
     kms_all = {}
-    if hip:
+    if prof:
         # per-kernel times of every kernel from a short untimed pass; inside the timed region only the three modelled kernels (lq, riccati, wbc — the roofline's
         # avg_launch_ms) carry HIP-event spans: two event records cost about one launch, 22 of them per step would cost 2 % of the headline
         itf.set_profiling(True); itf.reset_kernel_ms()
@@ -166,17 +202,19 @@ def run(args, make_engine=HipEngine, backend="nccl", device="cuda"):
         itf.set_profiling(span_level); itf.reset_kernel_ms()
     elapsed, mine = timed_region(eng, args.steps, dist, device)
     kms = {}
-    if hip:
+    if prof:
         itf.set_profiling(False)      # per-kernel HIP-event times over the timed region (events recorded on the stream each kernel runs on)
         kms = {k: (lq_both() if k == "lq" else (itf.kernel_ms(k) if span_level == 2 else kms_all[k])) for k in ("lq", "riccati", "wbc")}
     res = eng.results()
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, eng.outputs(), rank, world)
     avg = lambda k: (kms[k][0] / max(1, kms[k][1])) if k in kms else 0.0
     # every rank's {seconds of the timed region, avg launch ms of the modelled kernels, all statuses ok, intervals per launch}: what RCCL is used for here
     per_rank = sharding.gather_rows(np.array([[mine, avg("lq"), avg("riccati"), avg("wbc"), float(res["ok"]), float(res["n_intervals"])]]), dist, device)
 
     # ---- secondary figures (NOT the headline value) ----
     sec = {}
-    if hip and not args.no_secondary:
+    if prof and not args.no_secondary:
         sec = secondary_figures(args, eng, cfg, dist, device, world, rank)
 
     line = None
@@ -192,7 +230,7 @@ def run(args, make_engine=HipEngine, backend="nccl", device="cuda"):
         roofline = None; roofs = {}; flops_stale = traffic_stale = None
         from qm_control_amd import record_model as _rm
         src_hash = _rm.kernel_source_hash()
-        if hip:
+        if prof:
             roofs = {k: roof(k) for k in KM}
             # flops the kernels ISSUE, from the SQ instruction counters of this same command (tools/gpu_round_profile.sh -> profiles/flops_pmc.json: a STATIC file of the
             # named profile round, PMC collection cannot run inside the timed bench).  When present it REPLACES the survey's dense estimate as the kernel's flop count:
@@ -255,14 +293,17 @@ def run(args, make_engine=HipEngine, backend="nccl", device="cuda"):
             "per_rank": {"seconds": [float(v) for v in per_rank[:, 0]], "lq_ms": [float(v) for v in per_rank[:, 1]], "riccati_ms": [float(v) for v in per_rank[:, 2]],
                          "wbc_ms": [float(v) for v in per_rank[:, 3]], "intervals_per_launch": [int(v) for v in per_rank[:, 5]]},
         }
-        if hip:
+        if not prof:      # no per-kernel times in a plain run
+            for k in ("lq_ms", "riccati_ms", "wbc_ms"):
+                del line["per_rank"][k]
+        else:
             line["roofline"] = roofline
             line["fp64_peak_measured"] = {"mfma_f64_16x16x4": peak_mfma, "vector_fma": peak_fma, "unit": "TFLOP/s", "note": "roofline.peak stays the 78.6 TFLOP/s data-sheet figure"}
             keys = ("avg_launch_ms", "flop_per_launch", "tflops", "frac_fp64", "survey_dense_flop_per_launch", "survey_dense_frac_fp64", "bytes_per_launch", "tbs", "frac_hbm", "valu_non_f64_share")
             line["roofline_all"] = {k: {kk: v[kk] for kk in keys if kk in v} for k, v in roofs.items()}
             line["kernel_ms_per_step"] = {k: v[0] / 5 for k, v in kms_all.items()}
         line.update(sec)
-        if hip and not args.no_cpu_baseline and world == 1:      # the CPU baseline is a property of the box: reported on the single-GPU line only
+        if prof and not args.no_cpu_baseline and world == 1:      # the CPU baseline is a property of the box: reported on the single-GPU line only
             line["cpu_baseline"] = cpu_baseline(cfg, res["out"], B)
     eng.close()
     if dist is not None:

@@ -39,6 +39,12 @@ class EmuEngine:
         status = self.e.buf("status", (self.B,), np.int32)
         return dict(ok=bool((status == 0).all() and (self.st == 0).all()), out=self.out, n_intervals=n_intervals, ls_trials=0)
 
+    def outputs(self):
+        """the per-instance / per-node split of HipEngine.outputs, on what the emulated step leaves in host memory"""
+        n = self.e.buf("n_nodes", (self.B,), np.int32); ev = self.e.node_arr("node_ev", 1, np.int32).T
+        ev = np.where(np.arange(ev.shape[1])[None, :] < n[:, None], ev, 0)
+        return dict(num_nodes=n, status=self.e.buf("status", (self.B,), np.int32), wbc_out=self.out, wbc_qp_status=self.st), dict(event=ev)
+
     def close(self):
         pass
 

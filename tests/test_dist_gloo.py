@@ -23,13 +23,13 @@ def test_shard_bounds():
 
 
 @pytest.mark.parametrize("mode", ["weak", "strong"])
-def test_bench_code_path_two_ranks_over_gloo(oracle, mode):
+def test_bench_code_path_two_ranks_over_gloo(oracle, mode, tmp_path):
     """weak: --batch B per rank (the default headline); strong: --global-batch 2 B cut into two contiguous shards — the same instances either way"""
     import emu_harness
     emu_harness.build()                                                    # once, before two ranks race for the build
     B, N, K, W = 2, 8, 2, 1
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "tests", "dist_bench_driver.py"), "--gpus", "2", "--steps", str(K), "--warmup", str(W)] + (["--batch", str(B)] if mode == "weak" else ["--global-batch", str(2 * B)]) + ["--n-intervals", str(N), "--no-cpu-baseline", "--no-secondary"]
+           os.path.join(ROOT, "tests", "dist_bench_driver.py"), "--gpus", "2", "--steps", str(K), "--warmup", str(W)] + (["--batch", str(B)] if mode == "weak" else ["--global-batch", str(2 * B)]) + ["--n-intervals", str(N), "--no-cpu-baseline", "--no-secondary", "--dump-outputs", str(tmp_path)]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     payload = [l for l in p.stdout.splitlines() if l.startswith("BENCH_LINE ")]
@@ -50,3 +50,9 @@ def test_bench_code_path_two_ranks_over_gloo(oracle, mode):
     assert bad == 0 and allw.shape == (2 * B, 54)
     for b in range(2 * B):
         assert_blocks(allw[b], w[b], "wbc", 1e-6, b)
+    # --dump-outputs: every rank writes the last timed step's outputs of its own shard, as float64
+    dumped = [np.load(str(tmp_path / ("rank%d_wbc_out.npy" % r))) for r in range(2)]
+    assert all(d.dtype == np.float64 for d in dumped) and np.array_equal(np.concatenate(dumped), allw)
+    for r in range(2):
+        n, ev, idx = (np.load(str(tmp_path / ("rank%d_%s.npy" % (r, k)))) for k in ("num_nodes", "event", "node_sample_instances"))
+        assert np.array_equal(idx, np.arange(B)) and ev.shape[0] == B and (n > N).all() and not ev[:, int(n.max()):].any()

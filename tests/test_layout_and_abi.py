@@ -5,7 +5,7 @@ import re
 import numpy as np
 from qm_control_amd import layout as L
 import pytest
-from conftest import ROOT, REFERENCE
+from conftest import ROOT
 
 
 def _defines(path):
@@ -81,14 +81,18 @@ def test_oracle_blobs_come_from_the_numpy_front_end_and_check_the_product(blobs,
         assert blobs[1][front.ST[k]] == oblobs[1][front.ST[k]], k
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference not present")
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
 def test_shipped_inputs_and_gaits_are_the_reference_files():
-    import filecmp, front
+    """tests/data holds the reference's input files byte for byte (their sha256, recorded from the reference tree in tests/golden/reference_inputs.json), and the
+    shipped trot template is the one of the reference's gait.info (a copy: tests/golden/reference_gait.info)"""
+    import hashlib, json, front
     from qm_control_amd import scenarios
-    ref = [REFERENCE + "/qm_description/urdf/qudraputed_manipulator/robot.urdf", REFERENCE + "/qm_controllers/config/task.info", REFERENCE + "/qm_controllers/config/reference.info"]
-    for a, b in zip(INPUTS, ref):
-        assert filecmp.cmp(a, b, shallow=False), a
-    times, modes = front.load_gait(REFERENCE + "/qm_controllers/config/gait.info", "trot")
+    rec = json.load(open(os.path.join(GOLDEN, "reference_inputs.json")))["files"]
+    for a in INPUTS:
+        assert hashlib.sha256(open(a, "rb").read()).hexdigest() == rec[os.path.basename(a)]["sha256"], a
+    times, modes = front.load_gait(os.path.join(GOLDEN, "reference_gait.info"), "trot")
     g = scenarios.load_gaits()["trot"]
     assert times == g["switchingTimes"] and modes == g["modeSequence"]
 
@@ -120,13 +124,11 @@ def test_wbc_gain_names_of_the_reconfigure_server():
     for name in ("d_ee_x", "d_ee_y", "d_ee_z", "da_ee_z", "da_ee_y", "da_ee_x", "kp_arm_joint_7", "kp_arm_joint_0", "kp_ee_linear_w", "kp_swing_", "", "kp_arm_joint_11"):
         assert f(name.encode()) == -1, name
     assert f(None) == -1
-    # when the reference tree is present (this container, not the GPU box): the cfg file declares exactly these names + the six unread ones, with the blob's defaults
-    cfg = os.path.join("/root/reference", "qm_wbc", "cfg", "wbcWigeht.cfg")
-    if os.path.exists(cfg):
-        import re
-        from qm_control_amd import scenarios
-        st = scenarios.load_blobs()[1]
-        decl = dict((m.group(1), float(m.group(2))) for m in re.finditer(r'gen\.add\("(\w+)",\s*double_t,\s*0,\s*"[^"]*",\s*([-0-9.eE]+)', open(cfg).read()))
-        assert set(want) <= set(decl) and len(decl) == 38
-        for name, idx in want.items():
-            assert st[idx] == decl[name], name
+    # the reference's cfg file declares exactly these names + the six unread ones, with the blob's defaults (its declarations, recorded in tests/golden/reference_wbc_gains.json)
+    import json
+    from qm_control_amd import scenarios
+    st = scenarios.load_blobs()[1]
+    decl = dict((p["name"], float(p["default"])) for p in json.load(open(os.path.join(ROOT, "tests", "golden", "reference_wbc_gains.json")))["parameters"])
+    assert set(want) <= set(decl) and len(decl) == 38
+    for name, idx in want.items():
+        assert st[idx] == decl[name], name

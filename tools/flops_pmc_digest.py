@@ -10,8 +10,8 @@ import csv, json, os, re, sys
 
 
 def _stamp():
-    """hash of the kernel sources the profiled run was built from: written on the GPU box by tools/gpu_round_profile.sh (gpurun_out/kernel_source_hash.txt)"""
-    p = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "kernel_source_hash.txt")
+    """hash of the kernel sources the profiled run was built from: written by tools/gpu_round_profile.sh ($QM_PROFILE_OUT/kernel_source_hash.txt)"""
+    p = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.environ.get("QM_PROFILE_OUT", "profile_out"), "kernel_source_hash.txt")
     return open(p).read().strip() if os.path.exists(p) else None
 
 
