@@ -12,7 +12,6 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
-#include <functional>
 #include <vector>
 #include "../kernels/k_grid.h"
 #include "../kernels/k_lq.h"
@@ -76,13 +75,11 @@ struct QmMpcPipeline {
   bool r_force_dense = false;      // tests / A-B only (qmhip_debug_set "r_dense"): the dense instances run although R is block diagonal — same bits, by construction
   bool rblk() const { return r_blocks && !r_force_dense; }
   bool speculative_apply = true;   // tests only: false = the first trial's apply waits for the host's decision like every later one (A/B of the invariant below)
-  int lq_slices = 1;      // K1a / K1b run the horizon in this many node slices (1: one launch each)
   bool ipm_fresh = true;  // interior-point solver: the next iteration is the first of its solve (K0 ran): slack / dual / barrier parameter are initialised at the initial iterate
   int solved_B = 0;       // batch size of the last completed solve (0: none yet -> a warm start falls back to the cold start)
   int ncap = 0;           // nodes per instance the per-node launches of the current grid cover (0: not read back yet)
   bool ncap_pending = false;   // K0 has been launched and its count not been read yet
   bool has_m18 = true;         // some horizon of the current grid holds an all-stance phase (K0's conservative flag): K1b's second instance is launched
-  std::function<void()> before_lq;   // profiling only (co-residency probe): called right before the LQ kernel is launched
   const int* front_status = nullptr; int front_B = 0;   // sticky status of the device-resident GaitSchedule driving batches of front_B instances (null: schedules come from the host)
   explicit QmMpcPipeline(BK& b) : bk(b) {}
 
@@ -186,26 +183,11 @@ struct QmMpcPipeline {
     q.zvel = d.zvel; q.zpos = d.zpos; q.xref = d.xref; q.eeref = d.eeref; q.x = d.x; q.u = d.u; q.stage = d.stage; q.perf = d.perf; q.dbg = d.lqdbg; q.kin = d.kin; q.prof = lq_prof; q.ncap = ncap;
     q.ipm_s = d.ipm_s; q.ipm_l = d.ipm_l; q.ipm_info = d.ipm_info; q.rb = rblk() ? 1 : 0; q.single_mt = has_m18 ? 0 : 1;
     q.i0 = 0;
-    const int nsl = (ipm || d.lqdbg || lq_prof || lq_slices < 1) ? 1 : (lq_slices > ncap ? ncap : lq_slices);
-    if (nsl > 1) {
-      // node slices: kin records of a slice are written by K1a and read back by K1b before the next slice's records push them out of the memory-side cache
-      if (before_lq) before_lq();
-      for (int sidx = 0; sidx < nsl; ++sidx) {
-        const int a0 = (int)((long long)ncap * sidx / nsl), a1 = (int)((long long)ncap * (sidx + 1) / nsl); if (a1 <= a0) continue;
-        q.i0 = a0; q.ncap = a1 - a0;
-        bk.launch(qm_lq_kin_kernel, ((a1 - a0) * B + 63) / 64, 64, LQ_KIN_LDS_BYTES, q);
-        bk.launch(qm_lq_kernel, B * (a1 - a0), LW_BLOCK, LQ_LDS_BYTES, q);
-        if (has_m18) bk.launch(qm_lq_m18_kernel, B * (a1 - a0), LW_BLOCK, LQ_LDS_BYTES, q);
-      }
-      q.i0 = 0; q.ncap = ncap;
-    } else {
     bk.launch(qm_lq_kin_kernel, (nodes_threads + 63) / 64, 64, LQ_KIN_LDS_BYTES, q);
-    if (before_lq) before_lq();
     if (ipm) bk.launch(qm_lq_ipm_kernel, B * ncap, LW_BLOCK, LQ_LDS_BYTES, q);      // the interior-point instance: condensed inequality rows instead of the soft barrier costs
     else if (d.lqdbg || lq_prof) bk.launch(qm_lq_dbg_kernel, B * ncap, LW_BLOCK, LQ_LDS_BYTES, q);   // the instance with debug records / phase cycle stamps (parity tests, profiling)
     else { bk.launch(qm_lq_kernel, B * ncap, LW_BLOCK, LQ_LDS_BYTES, q);      // one wavefront per node: the nodes with m <= 16 reduced inputs (any gait phase with a swing leg) ...
            if (has_m18) bk.launch(qm_lq_m18_kernel, B * ncap, LW_BLOCK, LQ_LDS_BYTES, q); }  // ... and the stance nodes (m = 18): two instances of one body, three waves per SIMD each (k_lq.h)
-    }
     QmLsArgs l = ls_args(B); if (ilqr) { l.xt = d.xt; l.ut = d.ut; l.ilqr = 1; }
     if (ipm) { l.ipm_s = d.ipm_s; l.ipm_ds = d.ipm_ds; l.ipm_info = d.ipm_info; }
     QmRiccatiArgs r; r.B = B; r.nmax = d.nmax; r.n_nodes = d.n_nodes; r.node_ev = d.node_ev; r.x0 = d.x0; r.x = d.x; r.stage = d.stage; r.dx = d.dx; r.du = d.du; r.step_info = d.step_info; r.skip = riccati_skip;

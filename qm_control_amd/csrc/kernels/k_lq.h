@@ -49,8 +49,8 @@ struct QmLqArgs {
   double* dbg;               // optional [B][nmax][LQ_DBG_SIZE] unprojected LQ data (parity tests); may be null
   double* kin;               // [nmax][B][KR_SIZE] kin records (K1a -> K1b)
   int prof;                  // profiling only: thread 0 leaves phase cycle stamps in the (unused) SR_K field of the record
-  int ncap;                  // K1b: nodes per instance covered by the launch (the batch's largest node count, <= nmax; with node slices: the slice length)
-  int i0;                    // first node of the launch (node slices: K1a and K1b take the horizon in [i0, i0 + ncap) pieces so that a piece's kin records are consumed while they are still cached)
+  int ncap;                  // K1b: nodes per instance covered by the launch (the batch's largest node count, <= nmax)
+  int i0;                    // first node of the launch
   // interior-point instances only (k_ipm.h): slack / dual of the node's QM_NH inequality rows [nmax][B][QM_NH], barrier parameter per instance info[b * 8]
   const double* ipm_s; const double* ipm_l; const double* ipm_info;
   int single_mt;             // K1b product kernels: the host knows that NO node of the launch has more than 16 reduced inputs (K0 publishes it with the node capacity): qm_lq_kernel then takes every node without
@@ -387,11 +387,7 @@ __device__ __forceinline__ void qm_lq_body(QmLqArgs a) {
   // instrumented instance, profiling on: wave entry in shader-clock cycles and in ticks of the constant 100 MHz reference clock (tools/lq_residency_probe.py)
   const long long c0_ = (DBG && a.prof) ? (long long)__builtin_readcyclecounter() : 0; const long long r0_ = (DBG && a.prof) ? (long long)__builtin_amdgcn_s_memrealtime() : 0;
   const double* mb = qm_table(a.mb); const double* st = qm_table(a.st);
-#ifdef QM_LQ_FOLD_RECORDS      /* bandwidth experiment only (profiles/r06_ab_lq_write_bound.log): every wave writes its stage record into one of QM_LQ_FOLD_RECORDS slots — the stores stay in cache, the results are meaningless */
-  double* rec = a.stage + ((size_t)(blockIdx.x % QM_LQ_FOLD_RECORDS)) * SR_SIZE;
-#else
   double* rec = a.stage + ((size_t)b * a.nmax + i) * SR_SIZE;
-#endif
   double* dbg = (DBG && a.dbg) ? a.dbg + ((size_t)b * a.nmax + i) * LQ_DBG_SIZE : nullptr;
   const double* kr = a.kin + (size_t)nb * KR_SIZE;
   // every input address depends on (b, i) only: issue all loads before looking at the node's status (one memory round trip).  The node's status words are wave-uniform and

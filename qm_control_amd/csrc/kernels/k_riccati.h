@@ -38,7 +38,7 @@ struct QmRiccatiArgs {
   // baseline performance of the current iterate (sum of K1b's node terms) + arming of the line search, done by the instance's wave before the sweep
   // (what a separate one-wave-per-instance launch did: qm_perf_sum_kernel with with_alpha == 0); perf == nullptr: skipped
   const double* perf; double* base_sum; double* alpha; int* done; double* out_perf; int* open_cnt; int* tickets;
-  int skip;                                    // profiling only (bit mask: 1 Cholesky/solve, 2 matrix products, 4 forward, 8 symmetrise, 16 all regular backward stages, 64 lean operand prefetch (rw_prefetch), 256 no gain stores, 512 the rollout's fetch without its last two chunks, 128 nothing (the instrumented instance as it is): results are then
+  int skip;                                    // profiling only (bit mask: 1 Cholesky/solve, 2 matrix products, 4 forward, 8 symmetrise, 16 all regular backward stages, 128 nothing (the instrumented instance as it is): results are then
                                                // meaningless; 32: results intact, per-phase cycle counts are written to SR_K of each instance's first stage record)
 };
 
@@ -123,15 +123,11 @@ __device__ __forceinline__ void rw_prefetch_seg(const double* rec, qm_lds_ptr ld
     if ((t0 + 3) * 128 < LEN) qm_dma16_at<3072>(g, l3);
   }
 }
-// lean (profiling only, skip bit 64 of the instrumented instance): three of the twelve fragment chunks are NOT copied — the 360 doubles per stage that packed triangles of the
-// symmetric tiles Qp(0,0), Qp(1,1), Rp would save (round-5 review item 5).  The arithmetic then runs on stale operands (results meaningless); what is measured is the TIME
-// of a backward sweep that moves 7 % fewer bytes and pays nothing for unpacking them: the upper bound of what the packing could gain.
-__device__ __forceinline__ void rw_prefetch(const double* rec, double* lds_generic, int m, bool lean = false) {
+__device__ __forceinline__ void rw_prefetch(const double* rec, double* lds_generic, int m) {
   const qm_lds_ptr lds = qm_lds(lds_generic);
   const unsigned lane_bytes = 16u * (threadIdx.x & 63);
   rw_prefetch_seg<SR_AP, RPO_A, 360>(rec, lds, lane_bytes);
   rw_prefetch_seg<SR_BP, RPO_B, 216>(rec, lds, lane_bytes);
-  if (lean) rw_prefetch_seg<SR_FRAG, RPO_Q, SR_F_PP1 - 384>(rec, lds, lane_bytes); else
   rw_prefetch_seg<SR_FRAG, RPO_Q, SR_F_PP1>(rec, lds, lane_bytes);
   if (m > 16) rw_prefetch_seg<SR_FRAG + SR_F_PP1, RPO_Q + SR_F_PP1, SR_F_SIZE - SR_F_PP1>(rec, lds, lane_bytes);      // wave-uniform: the second tile row of the reduced inputs
   rw_prefetch_seg<SR_PX + 360, RPO_PX, 360>(rec, lds, lane_bytes);
@@ -241,7 +237,7 @@ __device__ __forceinline__ void rw_stage(double* rec, int m, const double* nrec,
 #pragma unroll
       for (int r = 0; r < 4; ++r) { Sn[0][0][r] = F[SR_F_QP + r * 64]; Sn[0][1][r] = F[SR_F_QP + (4 + r) * 64]; Sn[1][1][r] = F[SR_F_QP + (8 + r) * 64]; Sn[1][0][r] = 0.0; } }
     qm_lds_drain();
-    if (nrec) rw_prefetch(nrec, buf, mnext, PROF && (skip & 64));                        // next regular stage: flies during this stage's products and Cholesky
+    if (nrec) rw_prefetch(nrec, buf, mnext);                        // next regular stage: flies during this stage's products and Cholesky
   }
   RWT(0)
   qm_d4 SA[2][2], SB[2][MT];
@@ -437,13 +433,11 @@ __device__ __forceinline__ void rw_stage(double* rec, int m, const double* nrec,
         // record's profiling area nobody reads.  Rows m .. 15 exist in the record (the gain has 18 rows, the offset 18 entries) and are never read: their (finite) values
         // go out with the rest.  (Round 6: one lane-conditional region and one 64-bit address per element cost this lone wave ≈ 650 cycles per stage, 3 % of the sweep —
         // measured with the stores left out, profiles/r06_ab_riccati_dma.log)
-        if (!(PROF && (skip & 256))) {
-          double* p0 = rec + SR_PP + g * 30 + c;
-          double* p1 = (c < 14) ? rec + SR_PP + g * 30 + 16 + c : ((c == 14) ? rec + SR_KFF + g : rec + SR_K + 16 + g);
-          const int st1 = (c < 14) ? 120 : 4;
+        double* p0 = rec + SR_PP + g * 30 + c;
+        double* p1 = (c < 14) ? rec + SR_PP + g * 30 + 16 + c : ((c == 14) ? rec + SR_KFF + g : rec + SR_K + 16 + g);
+        const int st1 = (c < 14) ? 120 : 4;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) { p0[120 * r] = Kf[0][0][r]; p1[st1 * r] = Kf[0][1][r]; }
-        }
+        for (int r = 0; r < 4; ++r) { p0[120 * r] = Kf[0][0][r]; p1[st1 * r] = Kf[0][1][r]; }
       } else
 #pragma unroll
       for (int I = 0; I < MT; ++I)
@@ -453,7 +447,7 @@ __device__ __forceinline__ void rw_stage(double* rec, int m, const double* nrec,
 #pragma unroll
           for (int J = 0; J < 2; ++J) {
             const int col = 16 * J + c;
-            if (row < m && !(PROF && (skip & 256))) { if (col < 30) rec[SR_PP + row * 30 + col] = Kf[I][J][r]; else if (col == 30) rec[SR_KFF + row] = Kf[I][J][r]; }      // (skip bit 256, instrumented instance only: the gain is NOT stored — what the stores' acknowledgements cost the next stage's operand wait; results meaningless)
+            if (row < m) { if (col < 30) rec[SR_PP + row * 30 + col] = Kf[I][J][r]; else if (col == 30) rec[SR_KFF + row] = Kf[I][J][r]; }
           }
         } }
   } else rw_zero<MT, 2>(W);
@@ -606,9 +600,9 @@ __device__ __forceinline__ void qm_riccati_body(QmRiccatiArgs a) {
     for (int t0 = 0; t0 < 12; t0 += 4) {
       const qm_lds_ptr l3 = F + 1024 * t0;
       qm_dma16_at<0>((const char*)(rec + fsrc[t0]), l3); qm_dma16_at<1024>((const char*)(rec + fsrc[t0 + 1]), l3);
-      qm_dma16_at<2048>((const char*)(rec + fsrc[t0 + 2]), l3); if (!(PROF && (a.skip & 512) && t0 == 8)) qm_dma16_at<3072>((const char*)(rec + fsrc[t0 + 3]), l3);
+      qm_dma16_at<2048>((const char*)(rec + fsrc[t0 + 2]), l3); qm_dma16_at<3072>((const char*)(rec + fsrc[t0 + 3]), l3);
     }
-    if (fsrc[12] >= 0 && !(PROF && (a.skip & 512))) qm_dma16_at<0>((const char*)(rec + fsrc[12]), F + 1024 * 12);      // (skip bit 512, instrumented instance only: the rollout's fetch without its last two chunks — is the rollout bound by its bytes?)
+    if (fsrc[12] >= 0) qm_dma16_at<0>((const char*)(rec + fsrc[12]), F + 1024 * 12);
   };
   int cur = 0;
   { int k0 = 0; while (k0 < n - 1 && evlist(k0) == QM_EV_PRE) ++k0; if (k0 < n - 1 && !(a.skip & 4)) fetch(k0, 0); }

@@ -17,7 +17,6 @@ struct EmuBackend {
   void sync() {}
   void* alloc_mapped(size_t n, void** host_view) { void* p = malloc(n ? n : 8); *host_view = p; return p; }
   void free_mapped(void* p) { ::free(p); }
-  void wait_launched() {}
   void wait_flag(volatile int*, int) {}
   void wbc_inputs_next() {}
   void stream_select(int) {}
