@@ -44,6 +44,8 @@ class Oracle:
         L.qmo_create.argtypes = [_dp, _dp]
         L.qmo_swing_zvel.restype = C.c_double
         L.qmo_swing_zvel.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        L.qmo_swing_zpos.restype = C.c_double
+        L.qmo_swing_zpos.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.qmo_mode_at.argtypes = [C.c_void_p, C.c_double]
         L.qmo_destroy.argtypes = [C.c_void_p]
         self.mb = np.ascontiguousarray(model_blob, dtype=np.float64)
@@ -124,6 +126,9 @@ class Oracle:
     def swing_zvel(self, leg, t):
         return self.lib.qmo_swing_zvel(self.h, C.c_int(leg), C.c_double(t))
 
+    def swing_zpos(self, leg, t):
+        return self.lib.qmo_swing_zpos(self.h, C.c_int(leg), C.c_double(t))
+
     def mode_at(self, t):
         return self.lib.qmo_mode_at(self.h, C.c_double(t))
 
@@ -147,6 +152,13 @@ class Oracle:
         k = n.value
         return dict(t=nt[:k].copy(), ev=ne[:k].copy(), mode=nm[:k].copy(), x=xo[:k].copy(), u=uo[:k].copy(), perf=perf,
                     alpha=perf[8], armijo=perf[9], ls_trials=self.lib.qmo_ls_trials(self.h), warn=self.lib.qmo_last_warn(self.h))
+
+    def initial_guess(self):
+        """the initial guess the last mpc_step started from (cold: QMInitializer, warm: the previous solution interpolated): x [N+1][30], u [N][30]"""
+        x = np.zeros((self.MAXN, 30)); u = np.zeros((self.MAXN, 30))
+        n = self.lib.qmo_initial_guess(self.h, C.c_int(self.MAXN), _p(x), _p(u))
+        assert n >= 1, n
+        return x[:n].copy(), u[:n - 1].copy()
 
     def ls_trace(self):
         """diagnostics: rows {alpha, merit, theta, filter branch, accepted} of the last SQP iteration's line search; row 0 is the baseline {0, merit, theta0, armijo, -1}"""

@@ -57,6 +57,7 @@ void qmo_set_target(void* h, int K, const double* t, const double* x37) {
   for (int k = 0; k < K; ++k) o->P.target.x.emplace_back(x37 + QM_NREF * k, x37 + QM_NREF * (k + 1));
 }
 double qmo_swing_zvel(void* h, int leg, double t) { return ((Oracle*)h)->P.swing.zVel(leg, t); }
+double qmo_swing_zpos(void* h, int leg, double t) { return ((Oracle*)h)->P.swing.zPos(leg, t); }
 int qmo_mode_at(void* h, double t) { return ((Oracle*)h)->P.ms.modeAt(t); }
 void qmo_desired_state(void* h, double t, double* x37, double* eepos, double* eequat) {
   Oracle* o = (Oracle*)h; Vec r = o->P.target.desiredState(t); std::memcpy(x37, r.data(), QM_NREF * 8); o->P.target.eePose(t, eepos, eequat);
@@ -111,6 +112,13 @@ int qmo_ls_trials(void* h) { return ((Oracle*)h)->R.lsTrials; }
 int qmo_ls_trace(void* h, double* out, int max_rows) { const std::vector<double>& t = ((Oracle*)h)->R.lsTrace; const int n = (int)(t.size() / 5), k = n < max_rows ? n : max_rows; for (int i = 0; i < 5 * k; ++i) out[i] = t[i]; return k; }
 // tests only: 1 = every Jacobian from the full 60-slot forward mode of rounds 1-4 (the seeded evaluation must reproduce it entry by entry), 0 = seeded (default)
 void qmo_set_full_seeding(int on) { qm_ad_full_seeding = on != 0; }
+// tests: the initial guess of the last sqpIteration (x on the N + 1 nodes, u on the N intervals; PreEvent intervals carry zeros); returns N + 1, or -1 if maxn is too small
+int qmo_initial_guess(void* h, int maxn, double* x, double* u) {
+  const SqpResult& R = ((Oracle*)h)->R; const int n = (int)R.xGuess.size(); if (n > maxn) return -1;
+  for (int i = 0; i < n; ++i) std::memcpy(x + QM_NX * i, R.xGuess[i].data(), QM_NX * 8);
+  for (int i = 0; i + 1 < n; ++i) std::memcpy(u + QM_NU * i, R.uGuess[i].data(), QM_NU * 8);
+  return n;
+}
 int qmo_last_warn(void* h) { return ((Oracle*)h)->R.warn; }      // warning bits of the last (valid) solve: QM_MPC_WARN_PIVOT
 void qmo_phase_ms(void* h, double* ms3) { for (int i = 0; i < 3; ++i) ms3[i] = ((Oracle*)h)->R.phaseMs[i]; }
 // one more SQP iteration on the iterate the last call left (sqp.sqpIteration > 1, [upstream SqpSolver::runImpl loop]); same outputs as qmo_mpc_step

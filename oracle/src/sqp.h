@@ -106,6 +106,7 @@ struct SqpResult {
   std::vector<Vec> slack, dual, dslack, ddual; double barrier = 0.0, alphaPrimalMax = 1.0, alphaDualMax = 1.0, alphaDual = 0.0;
   std::vector<double> lsTrace;     // diagnostics: per line-search trial {alpha, merit, theta, filter branch (0: theta > gMax, 1: Armijo, 2: cost-or-constraint decrease), accepted}; [0..4] of the baseline: {0, merit, theta0, armijo, -1}
   double phaseMs[3] = {0, 0, 0};   // wall time of the last iteration: LQ approximation + projection, Riccati solve, line search (the timers ocs2's benchmark prints)
+  std::vector<Vec> xGuess, uGuess; // tests: the initial guess the iteration started from (initialGuess, cold or warm; the given iterate of an xInit/uInit call), u on the N intervals
 };
 
 // RK2 (Heun) flow value: x + dt/2 (k1 + k2)
@@ -283,6 +284,7 @@ inline void sqpIteration(const Problem& P, double t0, double tf, const Vec& x0, 
   std::vector<Vec> x(N + 1), u(N);
   if (xInit) { x = *xInit; u = *uInit; }
   else initialGuess(P, R, x0, prev, x, u);
+  R.xGuess = x; R.uGuess = u;
   // ---- setupQuadraticSubproblem ----
   const auto tq0 = std::chrono::steady_clock::now();
   R.lq.assign(N, NodeLQ()); Performance base;

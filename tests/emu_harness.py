@@ -81,6 +81,10 @@ class Emu:
         self.lib.emu_upload(self.h, C.c_int(B), _p(a("t0")), _p(a("x0")), _p(a("ref_t")), _p(a("ref_x")), _p(a("ev")), _pi(a("modes", np.int32)))
         self.lib.emu_grid(self.h, C.c_int(B), C.c_double(cfg["horizon"]))
 
+    def grid_warm(self, horizon):
+        """K0 warm-started from the resident solution (t0 / x0 as they are on the device, e.g. after advance); mpc_iterate then runs the iteration"""
+        self.lib.emu_grid_warm(self.h, C.c_int(self.B), C.c_double(horizon))
+
     def mpc_step_warm(self, t0, x0, horizon, max_trials=14):
         """new observation + warm-started SQP iteration (inputs / schedule of the last mpc_step stay resident)"""
         t0 = np.ascontiguousarray(t0, float); x0 = np.ascontiguousarray(x0, float)
