@@ -75,6 +75,7 @@ class QmhipSolver final : public ocs2::SolverBase {
   int lastStatus() const { return status_; }                          // 0 ok, > 0 warning bits on a valid solution (QM_MPC_WARN_PIVOT), < 0 failure; include/qmhip.h (qmhip_mpc_step)
   size_t warningCount() const { return warnings_; }                   // solves that completed with a warning since construction / reset
   const double* lastPerformance() const { return perf_; }             // baseline{merit,cost,dynSSE,eqSSE}, after{...}, alpha, armijo
+  void setStreamedIo(bool on) { streamed_ = on; }                     // false: warm calls go through qmhip_mpc_set_initial + qmhip_mpc_solve_resident_warm + qmhip_mpc_download again
 
  private:
   void runImpl(ocs2::scalar_t initTime, const ocs2::vector_t& initState, ocs2::scalar_t finalTime) override {
@@ -85,7 +86,7 @@ class QmhipSolver final : public ocs2::SolverBase {
     if (initState.size() != QM_NX) throw std::runtime_error("[QmhipSolver] state dimension must be 30");
     packSchedule(ms); packTargets(tt, initTime);
     const double t0 = initTime, horizon = finalTime - initTime;
-    int rc;
+    int rc; int32_t n = 0;
     // upload (it drops a previous solution only when the batch layout changes; the warm start below uses the one kept from the last call)
     const bool warm = havePrevious_;
     if (!warm) {
@@ -93,18 +94,31 @@ class QmhipSolver final : public ocs2::SolverBase {
       check(rc, "qmhip_mpc_upload");
       rc = qmhip_mpc_solve_resident(ctx_, 1, horizon);                  // cold start: QMInitializer (mpc.coldStart false only concerns later calls, task.info:142)
       check(rc, "qmhip_mpc_solve_resident");
+      rc = qmhip_mpc_download(ctx_, 1, &n, t_.data(), event_.data(), mode_.data(), x_.data(), u_.data(), perf_, &status_);
+      check(rc, "qmhip_mpc_download");
     } else {
       // schedule / targets may have changed since the last call: refresh them WITHOUT dropping the previous primal solution, then warm start from it
       rc = qmhip_mpc_update_references(ctx_, 1, sz_.maxRefKnots, refT_.data(), refX_.data(), sz_.maxEvents, ev_.data(), modes_.data());
       check(rc, "qmhip_mpc_update_references");
-      rc = qmhip_mpc_set_initial(ctx_, 1, &t0, initState.data());      // MPC_MRT_Interface::setCurrentObservation -> MPC_BASE::run(t, x)
-      check(rc, "qmhip_mpc_set_initial");
-      rc = qmhip_mpc_solve_resident_warm(ctx_, 1, horizon);
-      check(rc, "qmhip_mpc_solve_resident_warm");
+      if (streamed_) {
+        // the streamed step (include/qmhip.h): observation in through pinned staging (MPC_MRT_Interface::setCurrentObservation -> MPC_BASE::run(t, x)), warm-started
+        // solve, the record and the primal solution back in ONE copy behind ONE event.  No WBC here (QmhipWbc.h runs it on the control thread's own context), so
+        // period / time are not read
+        rc = qmhip_step_submit(ctx_, 1, &t0, initState.data(), nullptr, horizon, 1.0, t0, QMHIP_STEP_TRAJ);
+        check(rc, "qmhip_step_submit");
+        qmhip_step_record rec;
+        rc = qmhip_step_collect(ctx_, 1, &rec, t_.data(), event_.data(), mode_.data(), x_.data(), u_.data());
+        check(rc, "qmhip_step_collect");
+        n = rec.n_nodes; status_ = rec.mpc_status; for (int k = 0; k < 10; ++k) perf_[k] = rec.perf[k];
+      } else {      // the synchronous hand-over (about a dozen stream synchronisations per call): same bits, kept for A/B
+        rc = qmhip_mpc_set_initial(ctx_, 1, &t0, initState.data());
+        check(rc, "qmhip_mpc_set_initial");
+        rc = qmhip_mpc_solve_resident_warm(ctx_, 1, horizon);
+        check(rc, "qmhip_mpc_solve_resident_warm");
+        rc = qmhip_mpc_download(ctx_, 1, &n, t_.data(), event_.data(), mode_.data(), x_.data(), u_.data(), perf_, &status_);
+        check(rc, "qmhip_mpc_download");
+      }
     }
-    int32_t n = 0;
-    rc = qmhip_mpc_download(ctx_, 1, &n, t_.data(), event_.data(), mode_.data(), x_.data(), u_.data(), perf_, &status_);
-    check(rc, "qmhip_mpc_download");
     // Only FAILURES (< 0) throw — mpcThread_ answers an exception by stopping the controller (QMController.cpp:327-330).  A positive status is a warning on a valid solution:
     // QM_MPC_WARN_PIVOT = the observation time put a shooting node within weakEpsilon in front of a gait event (about once in 3700 calls at 100 Hz on ROS time) and the
     // zero-duration stage there was solved with zeroed pivots, like [upstream, recalled] HPIPM does — the reference's solver does not report that to its thread either.
@@ -145,7 +159,7 @@ class QmhipSolver final : public ocs2::SolverBase {
 
   qmhip_ctx* ctx_; Sizes sz_; const ocs2::OptimalControlProblem* problem_;
   std::vector<double> t_, x_, u_, ev_, refT_, refX_; std::vector<int32_t> event_, mode_, modes_;
-  double perf_[10] = {0}; int32_t status_ = 0; bool havePrevious_ = false; size_t warnings_ = 0;
+  double perf_[10] = {0}; int32_t status_ = 0; bool havePrevious_ = false, streamed_ = true; size_t warnings_ = 0;
   ocs2::PrimalSolution primal_; ocs2::PerformanceIndex performance_; std::vector<ocs2::PerformanceIndex> log_; size_t iterations_ = 0;
 };
 

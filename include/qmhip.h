@@ -201,6 +201,32 @@ int qmhip_hoqp_solve(qmhip_ctx* ctx, int B, int n_levels, int n, const int32_t* 
 int qmhip_control_step_resident(qmhip_ctx* ctx, int B, double horizon, double period, double time);
 int qmhip_wbc_download(qmhip_ctx* ctx, int B, double* out /*[B][54]*/, int32_t* qp_status /*[B][3]*/);
 
+/* ---- streamed control-step I/O: what a controller does per MPC call with its own plant on the host — MPC_MRT_Interface::setCurrentObservation + MPC_BASE::run +
+ *      evaluatePolicy + WbcBase::update (qm_controllers/src/QMController.cpp:133-148) — as a submit / collect pair that never stalls the device: the observation goes in
+ *      through pinned staging and asynchronous copies, the results of one instance come back as ONE fixed record (struct qmhip_step_record, qmhip_layout.h: policy at t0,
+ *      WBC output, perf, status words — 1024 bytes) packed on the device, and up to TWO steps may be in flight, so the record of step k travels while step k + 1 computes.
+ *      submit enqueues and returns; collect waits for the OLDEST step in flight only (one event of the copy stream; neither the MPC nor the WBC stream is synchronised).
+ *      submit = new observation (t0, x0) + one warm-started control step exactly as a step of qmhip_closed_loop_resident runs it (cold when no solution of this batch
+ *      exists: after qmhip_mpc_upload, qmhip_sim_reset, a solver switch): references and schedule are the resident ones — qmhip_mpc_upload / qmhip_mpc_update_references
+ *      or, when the gait front-end has been reset for this batch, its schedule refreshed before the solve.  Results are the bits of
+ *      qmhip_mpc_set_initial + qmhip_closed_loop_resident(n_steps 1) + qmhip_mpc_download + qmhip_wbc_download (tests/test_gpu_step_io.py).
+ *      flags: QMHIP_STEP_WBC runs the WBC and fills wbc_out / qp_status (zeros otherwise: K0, the SQP iterations and the policy at t0 only, the WBC's inputLast_
+ *      untouched); rbd_meas [B][55] is then the measured state and `time` its time (NULL: built from x0 as qmhip_control_step_resident does).  QMHIP_STEP_TRAJ also
+ *      returns the primal solution, compacted to the batch's largest node count on the device and copied with the records.
+ *      collect: rec [B]; trajectory outputs shaped like those of qmhip_mpc_download ([B][max_nodes][k]), any may be NULL: nodes 0 .. n_nodes[b] - 1 of instance b are written, the
+ *      caller's memory behind them is left untouched (qmhip_mpc_download writes all max_nodes).
+ *      Errors: a third submit while two steps are in flight, collect with nothing in flight, trajectory outputs for a step submitted without QMHIP_STEP_TRAJ, a WBC-only
+ *      context: QMHIP_ERR_STATE.  B other than the batch of the last qmhip_mpc_upload (or of the step being collected), B > max_batch, NULL t0 / x0 / rec, horizon or
+ *      period <= 0: QMHIP_ERR_ARG.  Any other entry point called while steps are in flight orders itself behind them as it does behind any enqueued step (its own
+ *      stream synchronisation or stream order); their records stay collectable. */
+#define QMHIP_STEP_WBC  1   /* run the WBC, fill wbc_out / qp_status */
+#define QMHIP_STEP_TRAJ 2   /* also return the primal solution */
+int qmhip_step_submit(qmhip_ctx* ctx, int B, const double* t0 /*[B]*/, const double* x0 /*[B][30]*/, const double* rbd_meas /*[B][55] or NULL*/,
+                      double horizon, double period, double time, unsigned flags);
+int qmhip_step_collect(qmhip_ctx* ctx, int B, qmhip_step_record* rec /*[B]*/,
+                       double* out_t /*[B][max_nodes]*/, int32_t* out_event, int32_t* out_mode, double* out_x /*[B][max_nodes][30]*/, double* out_u);
+int qmhip_step_in_flight(const qmhip_ctx* ctx);   /* 0, 1 or 2 */
+
 /* ---- batched rigid-body plant: stands where Gazebo + qm_gazebo::QMHWSim stand in the reference.
  *      sim_set_command = HybridJointHandle::setCommand as QMController::updateControlLaw issues it (qm_controllers/src/QMController.cpp:177-190):
  *        per joint posDes, velDes, kp, kd, ff in the reference's joint order (LF, LH, RF, RH, arm).

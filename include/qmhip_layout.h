@@ -153,4 +153,24 @@
 #define QM_EV_PRE  1
 #define QM_EV_POST 2
 
+/* record of one control step of one instance as qmhip_step_collect hands it over (qmhip.h, "streamed control-step I/O"): a fixed 1024 bytes, written on the device by
+   qm_step_pack_kernel (csrc/kernels/k_io.h) into an instance-major buffer that travels to the host in ONE copy.  QM_STEP_* are offsets in DOUBLES of the f64 part,
+   QM_STEP_I_* indices of the int32 words behind it (two 4-byte words per 8-byte slot) */
+#define QM_STEP_XDES    0    /* [30] policy state at t0                                                  */
+#define QM_STEP_UDES    30   /* [30] policy input at t0                                                  */
+#define QM_STEP_WBC     60   /* [54] WBC output [vdot(24), F(12), tau(18)]; zeros without QMHIP_STEP_WBC */
+#define QM_STEP_PERF    114  /* [10] perf of qmhip_mpc_download                                          */
+#define QM_STEP_DOUBLES 124
+#define QM_STEP_I_MODE   0   /* contact mode at t0                                                       */
+#define QM_STEP_I_STATUS 1   /* MPC status word as qmhip_mpc_download reports it                         */
+#define QM_STEP_I_NODES  2   /* number of nodes of the instance's grid                                   */
+#define QM_STEP_I_QP     3   /* [3] WBC status per priority level; zeros without QMHIP_STEP_WBC          */
+#define QM_STEP_INTS     8   /* 6, 7 reserved (0)                                                        */
+#define QM_STEP_BYTES 1024
+#include <stdint.h>
+typedef struct qmhip_step_record {
+  double x_des[30], u_des[30], wbc_out[54], perf[10];
+  int32_t mode, mpc_status, n_nodes, qp_status[3], reserved[2];
+} qmhip_step_record;
+
 #endif

@@ -25,7 +25,13 @@ EXPORTS = ["qmhip_create", "qmhip_create_from_blobs", "qmhip_create_wbc_context"
            "qmhip_get_kernel_ms", "qmhip_reset_kernel_ms", "qmhip_synchronize", "qmhip_last_ls_trials", "qmhip_debug_read", "qmhip_debug_set", "qmhip_debug_get", "qmhip_microbench_fp64",
            "qmhip_gait_set_templates", "qmhip_gait_reset", "qmhip_gait_insert_template", "qmhip_gait_update_resident", "qmhip_gait_download", "qmhip_schedule_download",
            "qmhip_target_reset", "qmhip_target_from_command", "qmhip_target_download",
+           "qmhip_step_submit", "qmhip_step_collect", "qmhip_step_in_flight",
            "qmhip_sim_set_params", "qmhip_sim_set_controller", "qmhip_sim_reset", "qmhip_sim_set_command", "qmhip_sim_step", "qmhip_sim_get_state", "qmhip_closed_loop_sim", "qmhip_closed_loop_sim_pipelined"]
+
+# struct qmhip_step_record (include/qmhip_layout.h) as a numpy structured dtype: one 1024-byte record per instance and control step
+STEP_WBC, STEP_TRAJ = 1, 2
+STEP_RECORD = np.dtype({"names": [f[0] for f in L.STEP_RECORD_FIELDS], "formats": [f[1] if f[2] == 1 else (f[1], (f[2],)) for f in L.STEP_RECORD_FIELDS],
+                        "offsets": [f[3] for f in L.STEP_RECORD_FIELDS], "itemsize": L.QM_STEP_BYTES})
 
 
 class QmhipError(RuntimeError):
@@ -226,6 +232,33 @@ class SqpMpc:
 
     def control_step_resident(self, horizon, period, time):
         self.itf._check(self.lib.qmhip_control_step_resident(self.itf.h, self.B, C.c_double(horizon), C.c_double(period), C.c_double(time)), "qmhip_control_step_resident")
+
+    def step_submit(self, t0, x0, rbd_meas=None, *, horizon, period, time, flags=STEP_WBC):
+        """streamed control step (qmhip_step_submit): new observation + one warm-started control step, enqueued and not waited for; at most two in flight.
+        rbd_meas [B][55]: the measured state the WBC runs on (None: built from x0 as control_step_resident does); flags: STEP_WBC | STEP_TRAJ"""
+        B = self.B; t0 = _f(t0, (B,)); x0 = _f(x0, (B, 30)); rbd = None if rbd_meas is None else _f(rbd_meas, (B, 55))
+        self.itf._check(self.lib.qmhip_step_submit(self.itf.h, B, _p(t0), _p(x0), _p(rbd), C.c_double(horizon), C.c_double(period), C.c_double(time), C.c_uint(flags)), "qmhip_step_submit")
+        self._step_flags = getattr(self, "_step_flags", []) + [int(flags)]
+
+    def step_collect(self, out=None):
+        """the oldest step in flight (qmhip_step_collect): the keys and shapes of download() + HierarchicalWbc.download() — num_nodes, perf, status, wbc_out, qp_status, plus
+        the policy at t0 (x_des, u_des, mode_t0) and the raw records (`record`, dtype STEP_RECORD); with STEP_TRAJ also t, event, mode, x, u [B][max_nodes][...], of which only
+        the first num_nodes[b] nodes are written (`out`: a dict of arrays to write into instead of fresh zeros)"""
+        B, nm = self.B, self.itf.max_nodes
+        flags = self._step_flags[0] if getattr(self, "_step_flags", None) else 0
+        rec = np.zeros(B, STEP_RECORD); res = {}
+        if flags & STEP_TRAJ:
+            out = out or {}
+            res = dict(t=out.get("t", np.zeros((B, nm))), event=out.get("event", np.zeros((B, nm), np.int32)), mode=out.get("mode", np.zeros((B, nm), np.int32)),
+                       x=out.get("x", np.zeros((B, nm, 30))), u=out.get("u", np.zeros((B, nm, 30))))
+        self.itf._check(self.lib.qmhip_step_collect(self.itf.h, B, rec.ctypes.data_as(C.c_void_p), _p(res.get("t")), _pi(res.get("event")), _pi(res.get("mode")), _p(res.get("x")), _p(res.get("u"))), "qmhip_step_collect")
+        self._step_flags.pop(0)
+        res.update(num_nodes=rec["n_nodes"].copy(), perf=rec["perf"].copy(), status=rec["mpc_status"].copy(), wbc_out=rec["wbc_out"].copy(), qp_status=rec["qp_status"].copy(),
+                   x_des=rec["x_des"].copy(), u_des=rec["u_des"].copy(), mode_t0=rec["mode"].copy(), record=rec)
+        return res
+
+    def steps_in_flight(self):
+        return int(self.lib.qmhip_step_in_flight(self.itf.h))
 
     def download(self):
         B, nm = self.B, self.itf.max_nodes

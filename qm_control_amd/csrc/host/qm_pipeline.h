@@ -49,7 +49,8 @@ struct QmMpcBuffers {
 // the warning QM_MPC_WARN_PIVOT, or -4 with ST_RICCATI_STRICT); bit 1 = a non-positive pivot on a stage of positive duration (Huu genuinely indefinite) or a pivot that is
 // not a number.  Bit 1, or a step that is not finite (a NaN in the observation reaches all three sums), is the hard failure -4: [upstream] SqpSolver throws on HPIPM's NaN
 // status, the controller stops (QMController.cpp:315-333) — never a policy made of NaNs behind a "valid solution" status.
-inline int qm_mpc_status(int k0_status, const double* step_info4, bool strict) {
+// Host and device run this one function: qmhip_mpc_download on the host, qm_step_pack_kernel (k_io.h) for the record of qmhip_step_collect.
+__host__ __device__ inline int qm_mpc_status(int k0_status, const double* step_info4, bool strict) {
   if (k0_status != 0) return k0_status;
   const double* s4 = step_info4; const int pv = (s4[3] == s4[3]) ? (int)s4[3] : 2;
   const bool finite = (s4[0] - s4[0] == 0.0) && (s4[1] - s4[1] == 0.0) && (s4[2] - s4[2] == 0.0);

@@ -17,6 +17,7 @@
 #include "qm_sim_pipeline.h"
 #include "qm_front_pipeline.h"
 #include "qm_hoqp_pipeline.h"
+#include "qm_io_pipeline.h"
 
 static thread_local std::string g_create_error;      // per calling thread: qmhip_last_error(NULL) is the error of THIS thread's last failed create
 
@@ -29,6 +30,7 @@ static thread_local std::string g_create_error;      // per calling thread: qmhi
 struct HipBackend {
   hipStream_t stream = nullptr;            // MPC stream (K0..K5); host copies
   hipStream_t stream_b = nullptr;          // WBC stream: the WBC of step k runs beside the MPC kernels of step k + 1 (the reference runs them in two threads too)
+  hipStream_t stream_c = nullptr;          // copy stream of the streamed step I/O (qm_io_pipeline.h): the record of step k travels to the host beside the kernels of step k + 1; carries copies only; created by the first qmhip_step_submit
   hipStream_t cur = nullptr;               // stream the next launch / memset goes to
   hipEvent_t ev_in = nullptr, ev_wbc = nullptr; bool wbc_pending = false;
   int profiling = 0;   // 0 off, 1 HIP-event span around every launch, 2 only around the modelled kernels (lq, riccati, wbc), 3 only around the LQ kernel (the dominant one: what the bench's timed region carries): two event records cost ≈ a launch
@@ -44,7 +46,7 @@ struct HipBackend {
     const void* p = (const void*)k;
     if (p == (const void*)qm_grid_kernel || p == (const void*)qm_grid_nodes_kernel || p == (const void*)qm_save_grid_kernel || p == (const void*)qm_advance_kernel) return "grid"; if (p == (const void*)qm_lq_kernel || p == (const void*)qm_lq_dbg_kernel || p == (const void*)qm_lq_ipm_kernel) return "lq"; if (p == (const void*)qm_lq_m18_kernel) return "lq_m18"; if (p == (const void*)qm_lq_kin_kernel) return "lq_kin"; if (p == (const void*)qm_riccati_kernel || p == (const void*)qm_riccati_prof_kernel) return "riccati";
     if (p == (const void*)qm_ls_eval_kernel || p == (const void*)qm_ls_eval_dense_kernel || p == (const void*)qm_ls_eval_ipm_kernel) return "ls_eval";
-    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel) return "rollout"; if (p == (const void*)qm_sim_kernel) return "sim"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_hoqp_kernel) return "hoqp";
+    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel) return "rollout"; if (p == (const void*)qm_sim_kernel) return "sim"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io";
     return "ls_misc";
   }
   template <class K, class A> void launch(K kernel, int grid, int block, size_t lds, const A& args) {
@@ -82,6 +84,20 @@ struct HipBackend {
   void copy_dd(void* d, const void* s, size_t n) { check(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, cur), "D2D"); }
   void* alloc_mapped(size_t n, void** host_view) { void* h = nullptr; void* dv = nullptr; check(hipHostMalloc(&h, n ? n : 8, hipHostMallocMapped), "hipHostMalloc"); check(hipHostGetDevicePointer(&dv, h, 0), "hipHostGetDevicePointer"); *host_view = h; return dv; }
   void free_mapped(void* host_view) { hipHostFree(host_view); }
+  // streamed step I/O (qm_io_pipeline.h): pinned staging, asynchronous copies, one event per slot
+  hipEvent_t ev_io_a = nullptr, ev_io_b = nullptr;
+  void* alloc_pinned(size_t n) { void* h = nullptr; check(hipHostMalloc(&h, n ? n : 8, hipHostMallocDefault), "hipHostMalloc"); return h; }
+  void free_pinned(void* p) { hipHostFree(p); }
+  void* io_event() { hipEvent_t e = nullptr; check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate"); return (void*)e; }
+  void io_event_free(void* e) { hipEventDestroy((hipEvent_t)e); }
+  void copy_in(void* d, const void* s, size_t n, int on) { check(hipMemcpyAsync(d, s, n, hipMemcpyHostToDevice, on ? stream_b : stream), "H2D"); }
+  void copy_out(void* d, const void* s, size_t n, void* done, bool wbc) {
+    if (!ev_io_a) { check(hipEventCreateWithFlags(&ev_io_a, hipEventDisableTiming), "hipEventCreate"); check(hipEventCreateWithFlags(&ev_io_b, hipEventDisableTiming), "hipEventCreate"); }
+    check(hipEventRecord(ev_io_a, stream), "hipEventRecord"); check(hipStreamWaitEvent(stream_c, ev_io_a, 0), "hipStreamWaitEvent");
+    if (wbc) { check(hipEventRecord(ev_io_b, stream_b), "hipEventRecord"); check(hipStreamWaitEvent(stream_c, ev_io_b, 0), "hipStreamWaitEvent"); }
+    check(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToHost, stream_c), "D2H"); check(hipEventRecord((hipEvent_t)done, stream_c), "hipEventRecord");
+  }
+  void io_wait(void* done) { check(hipEventSynchronize((hipEvent_t)done), "hipEventSynchronize"); }
   // wait for a host-visible word a kernel already launched on `cur` overwrites (anything but `pending`): a BOUNDED spin — a stream synchronisation costs 10-30 us of
   // wake-up latency, which matters for a line-search trial of a few tens of microseconds, but a solve must not hold a host core beside the ros_control thread for its
   // whole length — of at most spin_us microseconds (the trial kernels of a 1024-batch take ≈ 0.25 ms), then the stream synchronisation
@@ -105,13 +121,14 @@ struct HipBackend {
 struct qmhip_ctx {
   int device = 0, max_batch = 0, max_nodes = 0, max_ref = 0, max_ev = 0;
   double mb[MB_SIZE], st[ST_SIZE];
-  HipBackend bk; QmMpcPipeline<HipBackend> mpc; QmWbcPipeline<HipBackend> wbc; QmFrontPipeline<HipBackend> front; QmSimPipeline<HipBackend> sim; QmHoqpPipeline<HipBackend> hoqp;
+  HipBackend bk; QmMpcPipeline<HipBackend> mpc; QmWbcPipeline<HipBackend> wbc; QmFrontPipeline<HipBackend> front; QmSimPipeline<HipBackend> sim; QmHoqpPipeline<HipBackend> hoqp; QmIoPipeline<HipBackend> io;
   std::recursive_mutex mu;      // serialises the entry points of this context
   bool wbc_only = false;        // created by qmhip_create_wbc_context: carries the model + the WBC buffers, no horizon buffers
   void* dl_dev = nullptr; void* dl_pin = nullptr; size_t dl_cap = 0;      // staging of qmhip_mpc_download (device transpose buffer + its pinned host mirror), allocated on first use
   char* tick_pin = nullptr;     // pinned host staging of the control-tick path (qmhip_wbc_step): [inputs of max_batch instances | outputs]
   std::string error; int lastB = 0; bool have_solution = false; int front_B = 0; long sim_ticks = 0;
-  qmhip_ctx() : mpc(bk), wbc(bk), front(bk), sim(bk), hoqp(bk) {}
+  hipEvent_t ev_meas = nullptr; bool meas_pending = false;      // streamed step I/O: "the synthetic measured state of the last submitted step has read x0" (the next submit's copy of x0 waits for it on the device)
+  qmhip_ctx() : mpc(bk), wbc(bk), front(bk), sim(bk), hoqp(bk), io(bk) {}
   void fail(const std::string& m) { error = m; }
   // getModeSchedule on the device GaitSchedule -> the solver's schedule buffers; from here on its sticky status speaks for the schedule of this batch (until the host supplies one)
   void gait_schedule(int B, double horizon) { front.gait_schedule(mpc.d, B, horizon); mpc.front_status = front.f.gs_status; mpc.front_B = B; }
@@ -124,8 +141,11 @@ struct qmhip_ctx {
   //   MPC stream: K0 .. K4; the kernels that DECIDE the step length also write the policy at t0 (what evaluatePolicy(t0) reads from x + alpha dx)
   //   WBC stream: waits for that decision, then the WBC;   MPC stream: the batch's apply (the primal solution on every node) runs beside it, then the next step
   // Rounds 1-5 had apply -> policy kernel -> WBC on the critical path: 2 launches and ~ 60 us of a 2.7 ms step.
-  void control_step(int B, double horizon, double period, double time, bool warm) {
-    bk.stream_order(0, 1); bk.cur = bk.stream_b; wbc.measured_from_x0(mpc.d, B, time); bk.cur = bk.stream;      // (x0 is final on the MPC stream at this point; the previous WBC on this stream has read its rbd)
+  // streamed (qmhip_step_submit only): the caller's x0 arrives by an asynchronous copy, so the step notes when its measured-state kernel has read x0; meas_given: the
+  // caller supplied the measured state (already on its way into w.rbd / w.time on the WBC stream) — no synthetic one
+  void control_step(int B, double horizon, double period, double time, bool warm, bool streamed = false, bool meas_given = false) {
+    if (!meas_given) { bk.stream_order(0, 1); bk.cur = bk.stream_b; wbc.measured_from_x0(mpc.d, B, time); bk.cur = bk.stream; }      // (x0 is final on the MPC stream at this point; the previous WBC on this stream has read its rbd)
+    if (streamed && !meas_given) { bk.check(hipEventRecord(ev_meas, bk.stream_b), "hipEventRecord"); meas_pending = true; }
     mpc.p0_x = wbc.w.x_des; mpc.p0_u = wbc.w.u_des; mpc.p0_mode = wbc.w.mode;
     mpc.grid(B, horizon, warm);
     for (int it = 0, ni = sqp_iterations(); it < ni; ++it) { const bool last_it = it + 1 == ni; mpc.p0_enable = fused_policy && last_it; mpc.defer_apply = fused_policy && last_it; mpc.sqp_iteration(B, 14, last_it); }
@@ -133,6 +153,14 @@ struct qmhip_ctx {
     if (!mpc.p0_done) { mpc.apply_pending(); bk.wbc_inputs_next(); wbc.policy_eval_at_t0(mpc.d, B); }      // iLQR / interior-point solver / host-driven line search: the policy kernel on the applied primal solution
     bk.wbc_begin(); wbc.step(mpc.d, B, period, 0); bk.wbc_end();
     mpc.apply_pending();
+  }
+  // the MPC half of a control step alone (qmhip_step_submit without QMHIP_STEP_WBC): K0, the SQP iterations, the policy at t0 — no measured state, no WBC launch
+  void mpc_step(int B, double horizon, bool warm) {
+    mpc.p0_x = wbc.w.x_des; mpc.p0_u = wbc.w.u_des; mpc.p0_mode = wbc.w.mode;
+    mpc.grid(B, horizon, warm);
+    for (int it = 0, ni = sqp_iterations(); it < ni; ++it) { const bool last_it = it + 1 == ni; mpc.p0_enable = fused_policy && last_it; mpc.sqp_iteration(B, 14, last_it); }
+    mpc.p0_enable = false; lastB = B; have_solution = true;
+    if (!mpc.p0_done) { bk.wbc_inputs_next(); wbc.policy_eval_at_t0(mpc.d, B); }
   }
   int hipstate() { if (!bk.error.empty()) { error = bk.error; bk.error.clear(); return QMHIP_ERR_HIP; } return QMHIP_OK; }
 };
@@ -221,8 +249,8 @@ int qmhip_create_wbc_context(const qmhip_ctx* c, int max_batch, qmhip_ctx** out)
   return create_common(c->mb, c->st, c->device, max_batch, 3, 1, 1, out, true);      // same model / settings values, own device copies, own streams: nothing mutable is shared
 }
 void qmhip_destroy(qmhip_ctx* c) {
-  if (!c) return; hipSetDevice(c->device); c->bk.sync(); if (c->dl_dev) hipFree(c->dl_dev); if (c->dl_pin) hipHostFree(c->dl_pin); if (c->tick_pin) hipHostFree(c->tick_pin); c->mpc.release(); c->wbc.release(); c->front.release(); c->sim.release(); c->hoqp.release();
-  for (auto e : c->bk.pool) hipEventDestroy(e); if (c->bk.ev_order) hipEventDestroy(c->bk.ev_order); hipEventDestroy(c->bk.ev_in); hipEventDestroy(c->bk.ev_wbc); hipStreamDestroy(c->bk.stream); hipStreamDestroy(c->bk.stream_b); delete c;
+  if (!c) return; hipSetDevice(c->device); c->bk.sync(); if (c->bk.stream_c) hipStreamSynchronize(c->bk.stream_c); c->io.release(); if (c->ev_meas) hipEventDestroy(c->ev_meas); if (c->bk.ev_io_a) { hipEventDestroy(c->bk.ev_io_a); hipEventDestroy(c->bk.ev_io_b); } if (c->dl_dev) hipFree(c->dl_dev); if (c->dl_pin) hipHostFree(c->dl_pin); if (c->tick_pin) hipHostFree(c->tick_pin); c->mpc.release(); c->wbc.release(); c->front.release(); c->sim.release(); c->hoqp.release();
+  for (auto e : c->bk.pool) hipEventDestroy(e); if (c->bk.ev_order) hipEventDestroy(c->bk.ev_order); hipEventDestroy(c->bk.ev_in); hipEventDestroy(c->bk.ev_wbc); hipStreamDestroy(c->bk.stream); hipStreamDestroy(c->bk.stream_b); if (c->bk.stream_c) hipStreamDestroy(c->bk.stream_c); delete c;
 }
 // the text is copied under the context lock into a per-thread buffer: the pointer stays valid (until this THREAD's next qmhip_last_error) even if another thread's
 // failing call on the same context replaces the context's message meanwhile
@@ -430,6 +458,41 @@ int qmhip_control_step_resident(qmhip_ctx* c, int B, double horizon, double peri
   hipSetDevice(c->device); c->control_step(B, horizon, period, time, false);
   return c->hipstate();
 }
+
+// ---- streamed control-step I/O (include/qmhip.h): observation in, packed record out, two steps in flight ----
+// submit enqueues and returns: pinned staging -> asynchronous copies -> the control step as qmhip_closed_loop_resident runs it -> qm_step_pack_kernel (k_io.h) in order on
+// the stream(s) that produce what it reads -> ONE copy of the slot into its pinned mirror on the copy stream -> the slot's event.  collect waits for the oldest slot's
+// event only: the MPC and the WBC stream are never synchronised, so a step submitted meanwhile keeps running.
+int qmhip_step_submit(qmhip_ctx* c, int B, const double* t0, const double* x0, const double* rbd_meas, double horizon, double period, double time, unsigned flags) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c) return QMHIP_ERR_ARG;
+  if (B <= 0 || B > c->max_batch || B != c->lastB || !t0 || !x0 || !(horizon > 0) || !(period > 0) || (flags & ~(unsigned)(QMHIP_STEP_WBC | QMHIP_STEP_TRAJ))) {
+    c->fail("qmhip_step_submit: bad argument (B == batch of the last qmhip_mpc_upload, t0 / x0 not null, horizon > 0, period > 0, flags of QMHIP_STEP_*)"); return QMHIP_ERR_ARG; }
+  if (c->io.in_flight >= 2) { c->fail("qmhip_step_submit: two steps are in flight already (qmhip_step_collect the oldest first)"); return QMHIP_ERR_STATE; }
+  hipSetDevice(c->device); HipBackend& bk = c->bk; const bool wbc = (flags & QMHIP_STEP_WBC) != 0, traj = (flags & QMHIP_STEP_TRAJ) != 0;
+  if (!c->io.Bmax) { HIP_TRY(c, hipStreamCreate(&bk.stream_c)); HIP_TRY(c, hipEventCreateWithFlags(&c->ev_meas, hipEventDisableTiming)); c->io.allocate(c->max_batch); }      // first use: a context that never streams has the two streams it always had
+  QmIoSlot& s = c->io.next(); bk.cur = bk.stream;
+  if (c->meas_pending) { bk.check(hipStreamWaitEvent(bk.stream, c->ev_meas, 0), "hipStreamWaitEvent"); c->meas_pending = false; }
+  c->io.upload(s, c->mpc.d, c->wbc.w, B, t0, x0, wbc ? rbd_meas : nullptr, time);
+  if (c->front_B == B) c->gait_schedule(B, horizon);      // device-resident GaitSchedule active: modifyReferences before every MPC call, as qmhip_closed_loop_resident does
+  if (wbc) c->control_step(B, horizon, period, time, true, true, rbd_meas != nullptr); else c->mpc_step(B, horizon, true);      // warm when a solution of this batch exists (QmMpcPipeline::grid)
+  const int ncap = c->mpc.ncap > 0 && c->mpc.ncap <= c->max_nodes ? c->mpc.ncap : c->max_nodes;
+  c->io.reserve(s, QmIoPipeline<HipBackend>::slot_bytes(B, ncap, traj));
+  const bool strict = c->st[ST_RICCATI_STRICT] != 0.0;
+  c->io.pack(c->mpc.d, c->wbc.w, B, ncap, QM_PACK_MPC | (traj ? QM_PACK_TRAJ : 0) | (wbc ? 0 : QM_PACK_NOWBC), strict, s.dev);      // MPC stream: behind the batch's apply, in front of the next K0
+  if (wbc) { bk.cur = bk.stream_b; c->io.pack(c->mpc.d, c->wbc.w, B, ncap, QM_PACK_WBC, strict, s.dev); bk.cur = bk.stream; }      // WBC stream: behind this step's WBC, in front of the next
+  c->io.download(s, B, ncap, flags, traj, wbc);
+  return c->hipstate();
+}
+int qmhip_step_collect(qmhip_ctx* c, int B, qmhip_step_record* rec, double* ot, int32_t* oev, int32_t* omode, double* ox, double* ou) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c) return QMHIP_ERR_ARG;
+  if (c->io.in_flight == 0) { c->fail("qmhip_step_collect: no step in flight"); return QMHIP_ERR_STATE; }
+  const QmIoSlot& s = c->io.front();
+  if (B != s.B || !rec) { c->fail("qmhip_step_collect: bad argument (B == batch of the oldest step in flight, rec not null)"); return QMHIP_ERR_ARG; }
+  if ((ot || oev || omode || ox || ou) && !(s.flags & QMHIP_STEP_TRAJ)) { c->fail("qmhip_step_collect: trajectory outputs requested, but the step was submitted without QMHIP_STEP_TRAJ"); return QMHIP_ERR_STATE; }
+  hipSetDevice(c->device); c->io.collect(rec, c->max_nodes, ot, oev, omode, ox, ou);
+  return c->hipstate();
+}
+int qmhip_step_in_flight(const qmhip_ctx* c) { QM_GUARD(c); return c ? c->io.in_flight : 0; }
 
 // ---- batched rigid-body plant (QMHWSim.cpp:60-116) ----
 int qmhip_sim_set_params(qmhip_ctx* c, const double* p, int n) { QM_GUARD(c); QM_NEED_MPC(c);

@@ -15,3 +15,9 @@ with open(_HDR) as _fh:
         if _m:
             DEFINES[_m.group(1)] = float(_m.group(2))
 globals().update(DEFINES)
+
+# struct qmhip_step_record (include/qmhip_layout.h): (field, numpy type, count, byte offset) — the offsets follow from the QM_STEP_* defines above
+STEP_RECORD_FIELDS = [("x_des", "<f8", 30, 8 * QM_STEP_XDES), ("u_des", "<f8", 30, 8 * QM_STEP_UDES), ("wbc_out", "<f8", 54, 8 * QM_STEP_WBC), ("perf", "<f8", 10, 8 * QM_STEP_PERF),
+                      ("mode", "<i4", 1, 8 * QM_STEP_DOUBLES + 4 * QM_STEP_I_MODE), ("mpc_status", "<i4", 1, 8 * QM_STEP_DOUBLES + 4 * QM_STEP_I_STATUS),
+                      ("n_nodes", "<i4", 1, 8 * QM_STEP_DOUBLES + 4 * QM_STEP_I_NODES), ("qp_status", "<i4", 3, 8 * QM_STEP_DOUBLES + 4 * QM_STEP_I_QP),
+                      ("reserved", "<i4", 2, 8 * QM_STEP_DOUBLES + 4 * (QM_STEP_I_QP + 3))]
