@@ -28,6 +28,7 @@ class QmhipController : public QMController {
   void setupMpc(ros::NodeHandle& controllerNh) override {
     const auto& o = hip_->deviceOptions();
     mpc_ = std::make_shared<QmhipMpc>(qmInterface_->mpcSettings(), hip_->hipContext(), QmhipSolver::Sizes{o.maxNodes, o.maxRefKnots, o.maxEvents}, &qmInterface_->getOptimalControlProblem());
+    static_cast<QmhipMpc*>(mpc_.get())->getSolverPtr()->setFeedbackPolicy(qmInterface_->sqpSettings().useFeedbackPolicy);      // task.info:89: LinearController instead of FeedforwardController
     rbdConversions_ = std::make_shared<ocs2::CentroidalModelRbdConversions>(qmInterface_->getPinocchioInterface(), qmInterface_->getCentroidalModelInfo());
     const std::string robotName = "qm", gaitName = "legged_robot";
     ros::NodeHandle nh;

@@ -11,7 +11,9 @@
 //
 // The primal solution handed back is exactly what [upstream] multiple_shooting::toPrimalSolution builds with useFeedbackPolicy false: time / state / input
 // trajectories on the solver's grid (pre-event inputs copied from the previous node, last input repeated — libqmhip already returns them that way),
-// post-event indices, the mode schedule and a FeedforwardController over (time, input).
+// post-event indices, the mode schedule and a FeedforwardController over (time, input).  With useFeedbackPolicy true (task.info:89; QmhipSolver::setFeedbackPolicy, set
+// from the loaded sqp::Settings in QmhipController::setupMpc) the controller is an ocs2::LinearController over the same time stamps instead: gains and biases from
+// qmhip_mpc_download_feedback (K = Px + Pu K_riccati, uff = u* - K x*; include/qmhip.h "feedback policy"), so MPC_MRT_Interface::evaluatePolicy(t, x) applies the feedback.
 #pragma once
 #include <memory>
 #include <stdexcept>
@@ -23,6 +25,7 @@
 #include "stubs/reference_stubs.h"
 #else
 #include <ocs2_core/control/FeedforwardController.h>
+#include <ocs2_core/control/LinearController.h>
 #include <ocs2_mpc/MPC_BASE.h>
 #include <ocs2_oc/oc_data/PrimalSolution.h>
 #include <ocs2_oc/oc_solver/SolverBase.h>
@@ -47,6 +50,16 @@ inline void toPrimalSolution(int numNodes, const double* t, const int32_t* event
   }
   out.modeSchedule_ = modeSchedule;
   out.controllerPtr_.reset(new ocs2::FeedforwardController(out.timeTrajectory_, out.inputTrajectory_));
+}
+// useFeedbackPolicy: the LinearController [upstream multiple_shooting::toPrimalSolution] builds from (time, uff, K), from the arrays of qmhip_mpc_download_feedback
+inline void setLinearController(int numNodes, const double* gain /*[numNodes][30][30]*/, const double* uff /*[numNodes][30]*/, ocs2::PrimalSolution& out) {
+  ocs2::vector_array_t bias; ocs2::matrix_array_t gains; bias.reserve(numNodes); gains.reserve(numNodes);
+  for (int i = 0; i < numNodes; ++i) {
+    ocs2::vector_t b(QM_NU); ocs2::matrix_t K(QM_NU, QM_NX);
+    for (int r = 0; r < QM_NU; ++r) { b(r) = uff[(size_t)i * QM_NU + r]; for (int c = 0; c < QM_NX; ++c) K(r, c) = gain[((size_t)i * QM_NU + r) * QM_NX + c]; }
+    bias.push_back(std::move(b)); gains.push_back(std::move(K));
+  }
+  out.controllerPtr_.reset(new ocs2::LinearController(out.timeTrajectory_, std::move(bias), std::move(gains)));
 }
 
 class QmhipSolver final : public ocs2::SolverBase {
@@ -75,6 +88,7 @@ class QmhipSolver final : public ocs2::SolverBase {
   int lastStatus() const { return status_; }                          // 0 ok, > 0 warning bits on a valid solution (QM_MPC_WARN_PIVOT), < 0 failure; include/qmhip.h (qmhip_mpc_step)
   size_t warningCount() const { return warnings_; }                   // solves that completed with a warning since construction / reset
   const double* lastPerformance() const { return perf_; }             // baseline{merit,cost,dynSSE,eqSSE}, after{...}, alpha, armijo
+  void setFeedbackPolicy(bool on) { feedback_ = on; }                 // sqp::Settings::useFeedbackPolicy (task.info:89): hand out a LinearController instead of a FeedforwardController
   void setStreamedIo(bool on) { streamed_ = on; }                     // false: warm calls go through qmhip_mpc_set_initial + qmhip_mpc_solve_resident_warm + qmhip_mpc_download again
 
  private:
@@ -125,6 +139,12 @@ class QmhipSolver final : public ocs2::SolverBase {
     if (status_ < 0) throw std::runtime_error("[QmhipSolver] MPC iteration failed with status " + std::to_string(status_));
     if (status_ > 0) ++warnings_;
     toPrimalSolution(n, t_.data(), event_.data(), x_.data(), u_.data(), ms, primal_);
+    if (feedback_) {      // gains of the solve that has just finished (nothing is in flight any more: the streamed step was collected above)
+      gain_.resize((size_t)sz_.maxNodes * QM_NU * QM_NX); uff_.resize((size_t)sz_.maxNodes * QM_NU);
+      rc = qmhip_mpc_download_feedback(ctx_, 1, gain_.data(), uff_.data());
+      check(rc, "qmhip_mpc_download_feedback");
+      setLinearController(n, gain_.data(), uff_.data(), primal_);
+    }
     performance_.merit = perf_[4]; performance_.cost = perf_[5]; performance_.dynamicsViolationSSE = perf_[6]; performance_.equalityConstraintsSSE = perf_[7];
     log_.assign(1, performance_); iterations_ = 1; havePrevious_ = true;
   }
@@ -158,8 +178,8 @@ class QmhipSolver final : public ocs2::SolverBase {
   void check(int rc, const char* what) const { if (rc != QMHIP_OK) throw std::runtime_error(std::string("[QmhipSolver] ") + what + ": " + qmhip_last_error(ctx_)); }
 
   qmhip_ctx* ctx_; Sizes sz_; const ocs2::OptimalControlProblem* problem_;
-  std::vector<double> t_, x_, u_, ev_, refT_, refX_; std::vector<int32_t> event_, mode_, modes_;
-  double perf_[10] = {0}; int32_t status_ = 0; bool havePrevious_ = false, streamed_ = true; size_t warnings_ = 0;
+  std::vector<double> t_, x_, u_, ev_, refT_, refX_, gain_, uff_; std::vector<int32_t> event_, mode_, modes_;
+  double perf_[10] = {0}; int32_t status_ = 0; bool havePrevious_ = false, streamed_ = true, feedback_ = false; size_t warnings_ = 0;
   ocs2::PrimalSolution primal_; ocs2::PerformanceIndex performance_; std::vector<ocs2::PerformanceIndex> log_; size_t iterations_ = 0;
 };
 

@@ -70,6 +70,15 @@ struct FeedforwardController : ControllerBase {
   vector_t computeInput(scalar_t, const vector_t&) override { return u_.empty() ? vector_t() : u_.front(); }
   scalar_array_t t_; vector_array_t u_;
 };
+struct matrix_t { matrix_t() = default; matrix_t(int r, int c) : rows_(r), cols_(c), d(static_cast<size_t>(r) * c, 0.0) {} double& operator()(int i, int j) { return d[static_cast<size_t>(i) * cols_ + j]; } int rows() const { return rows_; } int cols() const { return cols_; } int rows_ = 0, cols_ = 0; std::vector<double> d; };      // Eigen::MatrixXd stand-in
+using matrix_array_t = std::vector<matrix_t>;
+// [upstream ocs2_core/control/LinearController.h, recalled]: u(t, x) = bias(t) + gain(t) x, both interpolated linearly over the time stamps
+struct LinearController : ControllerBase {
+  LinearController(scalar_array_t t, vector_array_t bias, matrix_array_t gain) : timeStamp_(std::move(t)), biasArray_(std::move(bias)), gainArray_(std::move(gain)) {}
+  LinearController* clone() const override { return new LinearController(*this); }
+  vector_t computeInput(scalar_t, const vector_t&) override { return biasArray_.empty() ? vector_t() : biasArray_.front(); }
+  scalar_array_t timeStamp_; vector_array_t biasArray_; matrix_array_t gainArray_;
+};
 struct PrimalSolution {
   PrimalSolution() = default;
   PrimalSolution(const PrimalSolution& o) { *this = o; }
@@ -137,7 +146,7 @@ struct PinocchioEndEffectorKinematics {
   PinocchioEndEffectorKinematics(const PinocchioInterface&, const CentroidalModelPinocchioMapping&, std::vector<std::string>) {}
 };
 struct Initializer {};
-namespace sqp { struct Settings { int threadPriority = 0; }; }
+namespace sqp { struct Settings { int threadPriority = 0; bool useFeedbackPolicy = false; }; }      // (task.info:89)
 class SqpSolverStub final : public SolverBase {     // stands for ocs2::SqpSolver behind SqpMpc::getSolverPtr()
  public:
   void reset() override {}

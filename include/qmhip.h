@@ -165,6 +165,23 @@ int qmhip_target_download(qmhip_ctx* ctx, int B, double* ref_t /*[B][max_ref_kno
 /* ---- policy evaluation: replaces MPC_MRT_Interface::evaluatePolicy (call site QMController.cpp:139-142):
  *      linear interpolation of the last primal solution at time t[b] */
 int qmhip_policy_eval(qmhip_ctx* ctx, int B, const double* t, double* x_des /*[B][30]*/, double* u_des /*[B][30]*/, int32_t* mode /*[B]*/);
+/* ---- feedback policy: what the same call returns when task.info says `sqp.useFeedbackPolicy true` (task.info:89, settings slot ST_FEEDBACK_POLICY): evaluatePolicy is
+ *      given the MEASURED state (QMController.cpp:139-142) and the SQP hands out a LinearController u(t, x) = uff(t) + K(t) x instead of a FeedforwardController
+ *      ([upstream ocs2_sqp multiple_shooting::toPrimalSolution / LinearController::computeInput, recalled]).  Per node with an input of its own, from the LAST SQP iteration:
+ *      K = Px + Pu K_riccati (30 x 30; the Riccati gain remapped through the constraint projection), uff = u* − K x*; a PreEvent node and the terminal node carry the
+ *      pair of the node their input was copied from.  Bias and gain are interpolated linearly in time like the feed-forward policy.
+ *      policy_eval_feedback: u_des = the linear controller at (t[b], x[b]); x_des and mode as qmhip_policy_eval.  ALWAYS applies the feedback, whatever ST_FEEDBACK_POLICY
+ *        says (the slot steers the device loops around the plant, below); x == NULL: exactly qmhip_policy_eval.
+ *      mpc_download_feedback: what ocs2::LinearController holds — gain [B][max_nodes][30][30], uff [B][max_nodes][30], on the time stamps qmhip_mpc_download returns
+ *        (nodes behind an instance's grid: zeros); either may be NULL.  Assembled on the device on request only (a tick needs two nodes).
+ *      Both read the stage records of the last solve: valid from the end of a solve until the next solve on this context starts.  QMHIP_ERR_STATE before any solve (or
+ *      after an upload / reset / solver switch) and while a qmhip_step_submit is in flight; QMHIP_ERR_ARG with ST_SOLVER 1 (iLQR) or 3 (interior point): the
+ *      multiple-shooting slots 0 / 2 only — never a silently feed-forward answer.  A stage whose pivots were zeroed (QM_MPC_WARN_PIVOT) contributes the gain the
+ *      factorisation left there (zero rows of K_riccati).  qmhip_step_submit / _collect and qmhip_control_step_resident evaluate at t0 with the state the solve started
+ *      from, where x − x*_0 = 0: the two policies coincide there and those entry points do not depend on the slot. */
+int qmhip_policy_eval_feedback(qmhip_ctx* ctx, int B, const double* t /*[B]*/, const double* x /*[B][30] or NULL*/,
+                               double* x_des /*[B][30]*/, double* u_des /*[B][30]*/, int32_t* mode /*[B]*/);
+int qmhip_mpc_download_feedback(qmhip_ctx* ctx, int B, double* gain /*[B][max_nodes][30][30]*/, double* uff /*[B][max_nodes][30]*/);
 
 /* ---- WBC: replaces qm::WbcBase::update / HierarchicalWbc::update (qm_wbc/include/qm_wbc/WbcBase.h:31-32,
  *      qm_wbc/src/HierarchicalWbc.cpp:18-44; variant 1 = HierarchicalMpcWbc.cpp:18-34).
@@ -259,12 +276,15 @@ int qmhip_sim_get_state(qmhip_ctx* ctx, int B, double* q, double* v, double* tim
  *        updateControlLaw (QMController.cpp:177-190: legs kp 0 / kd 3 once time > 10, arm arm_kp / arm_kd, WBC torque as feed-forward), one
  *        simulation step.  Needs qmhip_mpc_upload (reference, schedule) and qmhip_sim_reset before; the tick counter restarts at sim_reset.
  *        The reference runs the MPC in its own thread; here it is synchronous with the tick that triggers it.  On the first tick after a reset the
- *        WBC's joint-acceleration state inputLast_ (WbcBase.cpp:212-213) is primed with the planned input (zero joint acceleration). */
+ *        WBC's joint-acceleration state inputLast_ (WbcBase.cpp:212-213) is primed with the planned input (zero joint acceleration).
+ *        ST_FEEDBACK_POLICY = 1 (sqp.useFeedbackPolicy): every tick evaluates the SQP's linear controller at its estimated centroidal state (the observation it builds for the
+ *        MPC) instead of the feed-forward policy, in both controller modes; 0 launches exactly the feed-forward loop.  Solver slots 1 / 3 with the slot set: QMHIP_ERR_ARG. */
 int qmhip_closed_loop_sim(qmhip_ctx* ctx, int B, int n_ticks, double period, int n_substeps, int mpc_every, double horizon, double arm_kp, double arm_kd);
 /*      closed_loop_sim_pipelined: the same loop with the MPC BESIDE the control ticks, like mpcThread_ beside QMController::update (QMController.cpp:315-332): the
  *        MPC call triggered at a tick observes the plant at that tick and computes on its own stream while the next mpc_every ticks run on the policy published
  *        before; its solution is published (MPC_MRT_Interface's policy buffer) when those ticks are done — a latency of one MPC period, deterministic instead of
- *        thread-timing dependent.  The first call after a reset is synchronous.  n_ticks and the tick counter must be multiples of mpc_every. */
+ *        thread-timing dependent.  The first call after a reset is synchronous.  n_ticks and the tick counter must be multiples of mpc_every.
+ *        The published policy is a copy of the primal solution and carries no gains: with ST_FEEDBACK_POLICY = 1 this loop returns QMHIP_ERR_ARG. */
 int qmhip_closed_loop_sim_pipelined(qmhip_ctx* ctx, int B, int n_ticks, double period, int n_substeps, int mpc_every, double horizon, double arm_kp, double arm_kd);
 
 /* ---- instrumentation (ocs2 benchmark::RepeatedTimer analogue, QMController.cpp:145-147,321-323) ----

@@ -137,7 +137,12 @@
 #define ST_IPM_DUAL_LB        1050 /* ipm.initialDualLowerBound                 */
 #define ST_IPM_SLACK_MARGIN   1051 /* ipm.initialSlackMarginRate                */
 #define ST_IPM_DUAL_MARGIN    1052 /* ipm.initialDualMarginRate                 */
-#define ST_SIZE       1056  /* 1053..1055 reserved */
+/* sqp.useFeedbackPolicy (task.info:89; shipped false).  1: the policy the MPC hands out is the SQP's LINEAR controller u(t, x) = uff(t) + K(t) x
+   ([upstream ocs2_sqp multiple_shooting::toPrimalSolution with feedback + LinearController, recalled]: K = Px + Pu K_riccati of the last QP, uff = u* − K x*) —
+   the device loops around the plant (qmhip_closed_loop_sim) then evaluate it at the tick's estimated state; 0: the feed-forward policy (u*(t)).  Multiple-shooting
+   slots only (ST_SOLVER 0 / 2); qmhip_policy_eval_feedback applies the feedback whatever this slot says (qmhip.h) */
+#define ST_FEEDBACK_POLICY    1053
+#define ST_SIZE       1056  /* 1054..1055 reserved */
 /* inequality rows of a shooting node under ST_SOLVER = 3, in this order: arm joint position boxes (joint k: lower z − lo, upper hi − z; rows 2k, 2k + 1; 12 rows), arm joint
    velocity boxes (rows 12 + 2k, 13 + 2k; 12 rows), friction cone of contact c (row 24 + c; inactive — slack 1, dual 0, no contribution — while the foot swings) */
 #define QM_NH 28

@@ -20,7 +20,7 @@ MB_SIZE, ST_SIZE = L.MB_SIZE, L.ST_SIZE
 
 EXPORTS = ["qmhip_create", "qmhip_create_from_blobs", "qmhip_create_wbc_context", "qmhip_destroy", "qmhip_last_error", "qmhip_parse_model", "qmhip_export_blobs",
            "qmhip_set_setting", "qmhip_wbc_gain_index", "qmhip_mpc_step", "qmhip_mpc_upload", "qmhip_mpc_solve_resident", "qmhip_mpc_set_initial", "qmhip_mpc_update_references", "qmhip_mpc_solve_resident_warm",
-           "qmhip_mpc_advance_resident", "qmhip_closed_loop_resident", "qmhip_mpc_download", "qmhip_policy_eval",
+           "qmhip_mpc_advance_resident", "qmhip_closed_loop_resident", "qmhip_mpc_download", "qmhip_policy_eval", "qmhip_policy_eval_feedback", "qmhip_mpc_download_feedback",
            "qmhip_wbc_step", "qmhip_wbc_reset", "qmhip_hoqp_solve", "qmhip_control_step_resident", "qmhip_wbc_download", "qmhip_set_profiling",
            "qmhip_get_kernel_ms", "qmhip_reset_kernel_ms", "qmhip_synchronize", "qmhip_last_ls_trials", "qmhip_debug_read", "qmhip_debug_set", "qmhip_debug_get", "qmhip_microbench_fp64",
            "qmhip_gait_set_templates", "qmhip_gait_reset", "qmhip_gait_insert_template", "qmhip_gait_update_resident", "qmhip_gait_download", "qmhip_schedule_download",
@@ -278,6 +278,24 @@ class SqpMpc:
         self.itf._check(self.lib.qmhip_policy_eval(self.itf.h, self.B, _p(t), _p(x), _p(u), _pi(mode)), "qmhip_policy_eval")
         return x, u, mode
 
+    def evaluate_policy(self, t, x=None):
+        """MPC_MRT_Interface::evaluatePolicy(t, x): with a measured state x [B][30] the SQP's linear controller u = uff(t) + K(t) x (qmhip_policy_eval_feedback: the policy
+        of `sqp.useFeedbackPolicy true`, applied whatever the settings slot says); x=None: the feed-forward policy, exactly evaluatePolicy(t).  Returns (x_des, u_des, mode)"""
+        if x is None:
+            return self.evaluatePolicy(t)
+        t = _f(t, (self.B,)); xm = _f(x, (self.B, 30))
+        xd = np.zeros((self.B, 30)); u = np.zeros((self.B, 30)); mode = np.zeros(self.B, np.int32)
+        self.itf._check(self.lib.qmhip_policy_eval_feedback(self.itf.h, self.B, _p(t), _p(xm), _p(xd), _p(u), _pi(mode)), "qmhip_policy_eval_feedback")
+        return xd, u, mode
+
+    def feedback(self):
+        """the linear controller of the last solve as ocs2::LinearController holds it (qmhip_mpc_download_feedback): (gain [B][max_nodes][30][30], uff [B][max_nodes][30]) on the
+        time stamps of download()["t"]; nodes behind an instance's grid hold zeros"""
+        B, nm = self.B, self.itf.max_nodes
+        gain = np.zeros((B, nm, 30, 30)); uff = np.zeros((B, nm, 30))
+        self.itf._check(self.lib.qmhip_mpc_download_feedback(self.itf.h, B, _p(gain), _p(uff)), "qmhip_mpc_download_feedback")
+        return gain, uff
+
 
 class HierarchicalWbc:
     """qm::HierarchicalWbc-shaped front: update(stateDesired, inputDesired, rbdStateMeasured, mode, period, time) -> [x(36); tau(18)]."""
@@ -331,14 +349,18 @@ class QMHWSim:
     readSim (rbd state in the estimator's layout, contact flags)."""
     PARAMS = ("contact_stiffness", "contact_damping", "friction", "friction_speed_eps", "foot_radius", "delay", "saturate_effort")
 
-    def __init__(self, interface, robust_grid=False, **params):
+    def __init__(self, interface, robust_grid=False, feedback_policy=False, **params):
         """robust_grid: opt into the SQP time grid's robust minimum step (ST_GRID_DT_MIN = QM_GRID_DT_MIN_ROBUST, include/qmhip_layout.h) — for long fixed-rate loops whose
-        1 ms observation raster can land within weakEpsilon of a gait event; the default keeps [upstream]'s 10 * limitEpsilon"""
+        1 ms observation raster can land within weakEpsilon of a gait event; the default keeps [upstream]'s 10 * limitEpsilon.
+        feedback_policy: ST_FEEDBACK_POLICY = 1 (`sqp.useFeedbackPolicy true`): the ticks of closed_loop() evaluate the SQP's linear controller at the estimated state; False
+        leaves the context's setting as its task file / blob has it"""
         self.itf = interface
         self.lib = interface.lib
         self.B = 0
         if robust_grid:
             interface.set_setting(L.ST_GRID_DT_MIN, L.QM_GRID_DT_MIN_ROBUST)
+        if feedback_policy:
+            interface.set_setting(L.ST_FEEDBACK_POLICY, 1.0)
         if params:
             self.set_params(**params)
 

@@ -286,6 +286,7 @@ bool buildSettingsBlob(const std::string& taskInfo, const double* mb, double* st
                      {"ipm.initialSlackMarginRate", ST_IPM_SLACK_MARGIN, 1e-2}, {"ipm.initialDualMarginRate", ST_IPM_DUAL_MARGIN, 1e-2}};
   for (const KVD& e : opt) { std::string ignored; if (!infoScalar(t, e.key, st[e.idx], ignored)) st[e.idx] = e.dflt; }
   { st[ST_IPM_PRIMAL_FOR_DUAL] = 1.0; const INode* n = t.get("ipm.usePrimalStepSizeForDual"); if (n && !n->value.empty()) st[ST_IPM_PRIMAL_FOR_DUAL] = (n->value == "true" || n->value == "1") ? 1.0 : 0.0; }      // a boolean key
+  { const INode* n = t.get("sqp.useFeedbackPolicy"); st[ST_FEEDBACK_POLICY] = (n && (n->value == "true" || n->value == "1")) ? 1.0 : 0.0; }      // task.info:89 (missing: sqp::Settings' default, false)
   if (!(st[ST_SQP_DT] > 0.0) || !(st[ST_SQP_DT] < 1.0e300)) { err = "INFO: sqp.dt must be a positive finite number"; return false; }   // K0 walks t0 + k dt up to the horizon
   // ipm.dt is validated where it is used: qmhip_set_setting(ST_SOLVER, 2) / (ST_IPM_DT, .) and K0's `sane` guard
   st[ST_GRID_DT_MIN] = QM_GRID_DT_MIN_UPSTREAM;         // [upstream] timeDiscretizationWithEvents' default dt_min = 10 * limitEpsilon

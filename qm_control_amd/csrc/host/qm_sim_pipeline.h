@@ -13,6 +13,7 @@ struct QmSimBuffers {
   // published policy (pipelined loop): what evaluatePolicy reads while the MPC writes its next solution — OCS2 guards this buffer with a mutex, here it is a copy
   int p_nmax = 0, p_nev = 0; double* p_xs = nullptr; double* p_us = nullptr; double* p_node_t = nullptr; int* p_node_ev = nullptr; int* p_n_nodes = nullptr; double* p_ev = nullptr; int* p_modes = nullptr;
   bool p_valid = false;
+  double* x_est = nullptr; double* t_est = nullptr;      // feedback policy: the tick's estimated centroidal state ([B][30]) on the ticks without an MPC call
 };
 
 template <class BK>
@@ -26,9 +27,9 @@ struct QmSimPipeline {
     s.Bmax = Bmax; s.q = A<double>((size_t)Bmax * 24); s.v = A<double>((size_t)Bmax * 24); s.time = A<double>(Bmax); s.cmd = A<double>((size_t)Bmax * (QM_SIM_CMD - 1));
     s.ring = A<double>((size_t)Bmax * QM_SIM_SLOTS * QM_SIM_CMD); s.ring_n = A<int>((size_t)Bmax * 2); s.rbd = A<double>((size_t)Bmax * QM_NRBD); s.contact = A<int>((size_t)Bmax * 4);
     s.force = A<double>((size_t)Bmax * 12); s.status = A<int>(Bmax);
-    s.arm_hold = A<double>((size_t)Bmax * 6); s.arm_last = A<double>((size_t)Bmax * 6);
+    s.arm_hold = A<double>((size_t)Bmax * 6); s.arm_last = A<double>((size_t)Bmax * 6); s.x_est = A<double>((size_t)Bmax * 30); s.t_est = A<double>(Bmax);
   }
-  void release() { void* ps[] = {s.q, s.v, s.time, s.cmd, s.ring, s.ring_n, s.rbd, s.contact, s.force, s.status, s.arm_hold, s.arm_last, s.p_xs, s.p_us, s.p_node_t, s.p_node_ev, s.p_n_nodes, s.p_ev, s.p_modes}; for (void* ptr : ps) if (ptr) bk.free(ptr); s = QmSimBuffers(); }
+  void release() { void* ps[] = {s.q, s.v, s.time, s.cmd, s.ring, s.ring_n, s.rbd, s.contact, s.force, s.status, s.arm_hold, s.arm_last, s.p_xs, s.p_us, s.p_node_t, s.p_node_ev, s.p_n_nodes, s.p_ev, s.p_modes, s.x_est, s.t_est}; for (void* ptr : ps) if (ptr) bk.free(ptr); s = QmSimBuffers(); }
   // "Simulation reset" of QMHWSim::writeSim: state set, delay buffer and held command cleared
   void reset(int B, const double* q_host, const double* v_host, const double* time_host) {
     s.p_valid = false;
@@ -48,6 +49,8 @@ struct QmSimPipeline {
   }
   // currentObservation_ of the MPC (x0, t0) from the plant state
   void observe(const QmMpcBuffers& d, int B) { QmObserveArgs o; o.mb = d.mb; o.B = B; o.rbd = s.rbd; o.time = s.time; o.x0 = d.x0; o.t0 = d.t0; bk.launch(qm_observe_kernel, (B + 63) / 64, 64, 0, o); }
+  // the same estimate on a tick between two MPC calls (feedback policy): the observation stays out of the solver's x0 / t0
+  void estimate(const QmMpcBuffers& d, int B) { QmObserveArgs o; o.mb = d.mb; o.B = B; o.rbd = s.rbd; o.time = s.time; o.x0 = s.x_est; o.t0 = s.t_est; bk.launch(qm_observe_kernel, (B + 63) / 64, 64, 0, o); }
   // hybrid joint command from the evaluated policy and the WBC torques
   void command(int B, const double* x_des, const double* u_des, const double* wbc_out, double arm_kp, double arm_kd) {
     QmCommandArgs c; c.B = B; c.x_des = x_des; c.u_des = u_des; c.wbc_out = wbc_out; c.time = s.time; c.arm_kp = arm_kp; c.arm_kd = arm_kd; c.cmd = s.cmd;
@@ -66,16 +69,21 @@ struct QmSimPipeline {
 // resident data: state estimate (the plant's state) -> every mpc_every ticks an MPC call on that observation (pre_mpc: the gait front-end's schedule refresh,
 // then a warm-started solve with sqp_iters SQP iterations) -> policy at the plant time -> WBC on the measured state -> hybrid joint command -> simulation step.
 // Shared by the product (qmhip_closed_loop_sim) and the host emulator of the tests.
+// feedback (ST_FEEDBACK_POLICY; multiple-shooting solvers only — the caller checks): the tick evaluates the SQP's linear controller at its estimated centroidal state
+// (evaluatePolicy(time, currentObservation_.state, ...), QMController.cpp:139-142, with sqp.useFeedbackPolicy) in place of the feed-forward policy: the observation the MPC
+// call of this tick was given, or the same estimate built for this tick alone
 template <class BK, class PreMpc>
 void qm_closed_loop_sim_ticks(BK& bk, QmMpcPipeline<BK>& mpc, QmWbcPipeline<BK>& wbc, QmSimPipeline<BK>& sim, long& sim_ticks, int B, int n_ticks, double period, int n_substeps,
-                              int mpc_every, double horizon, double arm_kp, double arm_kd, int sqp_iters, PreMpc pre_mpc) {
+                              int mpc_every, double horizon, double arm_kp, double arm_kd, int sqp_iters, PreMpc pre_mpc, bool feedback = false) {
   for (int k = 0; k < n_ticks; ++k) {
-    if ((sim_ticks % mpc_every) == 0) {
+    const bool mpc_tick = (sim_ticks % mpc_every) == 0;
+    if (mpc_tick) {
       sim.observe(mpc.d, B);
       pre_mpc();
       mpc.grid(B, horizon, true); for (int it = 0; it < sqp_iters; ++it) mpc.sqp_iteration(B, 14, it + 1 == sqp_iters);
     }
-    bk.launch(qm_policy_kernel, (B + 63) / 64, 64, 0, wbc.pargs(mpc.d, B, sim.s.time));
+    if (feedback) { if (!mpc_tick) sim.estimate(mpc.d, B); wbc.policy_fb(mpc.d, B, sim.s.time, mpc_tick ? mpc.d.x0 : sim.s.x_est); }
+    else bk.launch(qm_policy_kernel, (B + 63) / 64, 64, 0, wbc.pargs(mpc.d, B, sim.s.time));
     // first tick after a reset: inputLast_ primed with the planned input (the reference's WBC has been running since time 0 when the legs are switched on at
     // time 10): zero joint acceleration
     if (sim_ticks == 0) bk.copy_dd(wbc.w.input_last, wbc.w.u_des, (size_t)B * 30 * 8);

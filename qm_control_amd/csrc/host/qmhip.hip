@@ -46,7 +46,7 @@ struct HipBackend {
     const void* p = (const void*)k;
     if (p == (const void*)qm_grid_kernel || p == (const void*)qm_grid_nodes_kernel || p == (const void*)qm_save_grid_kernel || p == (const void*)qm_advance_kernel) return "grid"; if (p == (const void*)qm_lq_kernel || p == (const void*)qm_lq_dbg_kernel || p == (const void*)qm_lq_ipm_kernel) return "lq"; if (p == (const void*)qm_lq_m18_kernel) return "lq_m18"; if (p == (const void*)qm_lq_kin_kernel) return "lq_kin"; if (p == (const void*)qm_riccati_kernel || p == (const void*)qm_riccati_prof_kernel) return "riccati";
     if (p == (const void*)qm_ls_eval_kernel || p == (const void*)qm_ls_eval_dense_kernel || p == (const void*)qm_ls_eval_ipm_kernel) return "ls_eval";
-    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel) return "rollout"; if (p == (const void*)qm_sim_kernel) return "sim"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io";
+    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel) return "rollout"; if (p == (const void*)qm_sim_kernel) return "sim"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_policy_fb_kernel) return "policy_fb"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io";
     return "ls_misc";
   }
   template <class K, class A> void launch(K kernel, int grid, int block, size_t lds, const A& args) {
@@ -184,7 +184,7 @@ __global__ void qm_bench_mfma_kernel(double* out, int iters) {
 static bool setting_ok(int idx, double v) {
   if (idx == ST_SQP_DT || idx == ST_IPM_DT) return v > 0.0 && std::isfinite(v);
   if (idx == ST_GRID_DT_MIN) return v >= 0.0 && std::isfinite(v);
-  if (idx == ST_RICCATI_STRICT || idx == ST_IPM_PRIMAL_FOR_DUAL) return v == 0.0 || v == 1.0;
+  if (idx == ST_RICCATI_STRICT || idx == ST_IPM_PRIMAL_FOR_DUAL || idx == ST_FEEDBACK_POLICY) return v == 0.0 || v == 1.0;
   // interior-point solver (slot 3, k_ipm.h): the barrier parameter and the slack / dual floors are divided by and go through log(); the margin and the linear factor are fractions
   if (idx == ST_IPM_MU || idx == ST_IPM_MU_TARGET || idx == ST_IPM_SLACK_LB || idx == ST_IPM_DUAL_LB) return v > 0.0 && std::isfinite(v);
   if (idx == ST_IPM_FTB_MARGIN || idx == ST_IPM_MU_LINEAR) return v > 0.0 && v < 1.0;
@@ -203,6 +203,7 @@ static int create_common(const double* mb, const double* st, int device, int max
   // a blob of an older layout (no size / version stamp travels with it) would put garbage into the slots added since: check the ones a kernel's control flow depends on
   if (!setting_ok(ST_GRID_DT_MIN, st[ST_GRID_DT_MIN])) { g_create_error = "settings blob: the time grid's minimum step (ST_GRID_DT_MIN) must be a non-negative finite number - is the blob of an older layout (ST_SIZE)?"; return QMHIP_ERR_MODEL; }
   if (st[ST_RICCATI_STRICT] != 0.0 && st[ST_RICCATI_STRICT] != 1.0) { g_create_error = "settings blob: ST_RICCATI_STRICT must be 0 or 1 - is the blob of an older layout (ST_SIZE)?"; return QMHIP_ERR_MODEL; }
+  if (st[ST_FEEDBACK_POLICY] != 0.0 && st[ST_FEEDBACK_POLICY] != 1.0) { g_create_error = "settings blob: ST_FEEDBACK_POLICY must be 0 or 1 - is the blob of an older layout (ST_SIZE)?"; return QMHIP_ERR_MODEL; }
   if (st[ST_SOLVER] != 0.0 && st[ST_SOLVER] != 1.0 && st[ST_SOLVER] != 2.0 && st[ST_SOLVER] != 3.0) { g_create_error = "settings blob: ST_SOLVER must be 0, 1, 2 or 3"; return QMHIP_ERR_MODEL; }
   if (st[ST_SOLVER] == 3.0 && !ipm_settings_ok(st)) { g_create_error = "settings blob: ST_SOLVER = 3 needs the ipm block's slots (ST_IPM_*: barrier parameters, slack / dual floors > 0, margin and linear factor in (0, 1), power > 1) - is the blob of an older layout (ST_SIZE)?"; return QMHIP_ERR_MODEL; }
   int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_error = "no HIP device available (libqmhip has no CPU fallback)"; return QMHIP_ERR_HIP; }
@@ -270,7 +271,7 @@ int qmhip_wbc_gain_index(const char* name) {
 }
 int qmhip_set_setting(qmhip_ctx* c, int idx, double v) { QM_GUARD(c);
   if (!c || idx < 0 || idx >= ST_SIZE) return QMHIP_ERR_ARG;
-  if (!setting_ok(idx, v)) { c->fail("qmhip_set_setting: sqp.dt / ipm.dt must be a positive finite number, the grid's minimum step a non-negative one, ST_RICCATI_STRICT 0 or 1; ipm block: barrier parameters and slack / dual floors > 0, margin and linear decrease factor in (0, 1), superlinear power > 1, margin rates >= 0"); return QMHIP_ERR_ARG; }
+  if (!setting_ok(idx, v)) { c->fail("qmhip_set_setting: sqp.dt / ipm.dt must be a positive finite number, the grid's minimum step a non-negative one, ST_RICCATI_STRICT and ST_FEEDBACK_POLICY 0 or 1; ipm block: barrier parameters and slack / dual floors > 0, margin and linear decrease factor in (0, 1), superlinear power > 1, margin rates >= 0"); return QMHIP_ERR_ARG; }
   if (idx == ST_SOLVER && v == 3.0 && !ipm_settings_ok(c->st)) { c->fail("qmhip_set_setting: solver 3 needs valid ipm settings (ST_IPM_*) - is the settings blob of an older layout?"); return QMHIP_ERR_ARG; }
   if (idx == ST_SOLVER && v >= 2.0 && !setting_ok(ST_IPM_DT, c->st[ST_IPM_DT])) { c->fail("qmhip_set_setting: solvers 2 / 3 need a positive finite ipm.dt"); return QMHIP_ERR_ARG; }
   if (idx == ST_SOLVER) { if (v != 0.0 && v != 1.0 && v != 2.0 && v != 3.0) { c->fail("qmhip_set_setting: ST_SOLVER is 0 (SQP), 1 (discrete iLQR), 2 (the SQP step on the `ipm` block's parameters) or 3 (interior-point method with hard friction cones / arm boxes)"); return QMHIP_ERR_ARG; } c->mpc.solver = (int)v; c->mpc.solved_B = 0; c->have_solution = false; c->mpc.ipm_fresh = true; }      // (a solver switch starts the interior-point state over: slack / dual / barrier parameter of an earlier solve are not carried across)
@@ -410,6 +411,40 @@ int qmhip_policy_eval(qmhip_ctx* c, int B, const double* t, double* xd, double* 
   if (xd) c->bk.to_host(xd, c->wbc.w.x_des, (size_t)B * 30 * 8); if (ud) c->bk.to_host(ud, c->wbc.w.u_des, (size_t)B * 30 * 8); if (mode) c->bk.to_host(mode, c->wbc.w.mode, (size_t)B * 4);
   return c->hipstate();
 }
+// the feedback entry points read the stage records of the last SQP iteration: they exist for the multiple-shooting solver slots only, from the end of a solve until the
+// next one starts (K1b rewrites the records), and not while a streamed step is in flight (its solve may be rewriting them)
+static int feedback_ready(qmhip_ctx* c, int B, const char* fn) {
+  if (c->mpc.solver != 0 && c->mpc.solver != 2) { c->fail(std::string(fn) + ": the feedback policy exists for the multiple-shooting solver slots only (ST_SOLVER 0 / 2), not for the discrete iLQR (1) or the interior-point method (3)"); return QMHIP_ERR_ARG; }
+  if (c->io.in_flight > 0) { c->fail(std::string(fn) + ": a qmhip_step_submit is in flight (qmhip_step_collect it first: its solve rewrites the stage records the gains are read from)"); return QMHIP_ERR_STATE; }
+  if (!c->have_solution) { c->fail(std::string(fn) + ": no policy received yet (no solve on this context since its creation, the last upload, reset or solver switch)"); return QMHIP_ERR_STATE; }
+  if (B != c->mpc.solved_B) { c->fail(std::string(fn) + ": B differs from the batch size of the last solve"); return QMHIP_ERR_STATE; }
+  return QMHIP_OK;
+}
+int qmhip_policy_eval_feedback(qmhip_ctx* c, int B, const double* t, const double* x, double* xd, double* ud, int32_t* mode) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c || B <= 0 || B > c->max_batch || !t) { if (c) c->fail("qmhip_policy_eval_feedback: bad argument"); return QMHIP_ERR_ARG; }
+  if (!x) return qmhip_policy_eval(c, B, t, xd, ud, mode);
+  const int rc = feedback_ready(c, B, "qmhip_policy_eval_feedback"); if (rc != QMHIP_OK) return rc;
+  hipSetDevice(c->device); c->wbc.policy_eval_feedback(c->mpc.d, B, t, x);
+  if (xd) c->bk.to_host(xd, c->wbc.w.x_des, (size_t)B * 30 * 8); if (ud) c->bk.to_host(ud, c->wbc.w.u_des, (size_t)B * 30 * 8); if (mode) c->bk.to_host(mode, c->wbc.w.mode, (size_t)B * 4);
+  return c->hipstate();
+}
+int qmhip_mpc_download_feedback(qmhip_ctx* c, int B, double* gain, double* uff) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c || B <= 0 || B > c->max_batch) { if (c) c->fail("qmhip_mpc_download_feedback: bad argument"); return QMHIP_ERR_ARG; }
+  const int rc = feedback_ready(c, B, "qmhip_mpc_download_feedback"); if (rc != QMHIP_OK) return rc;
+  if (!gain && !uff) return QMHIP_OK;
+  hipSetDevice(c->device); const int nm = c->max_nodes;
+  // assembled on the device for a slice of the batch at a time (<= 64 MB of staging: one instance-node pair is 930 doubles), each slice one contiguous copy per array
+  const size_t per = (size_t)nm * 930 * 8; int nb = (int)((64u << 20) / per); nb = nb < 1 ? 1 : (nb > B ? B : nb);
+  double* stg = nullptr; HIP_TRY(c, hipMalloc((void**)&stg, (size_t)nb * per)); double* stg_u = stg + (size_t)nb * nm * 900;
+  for (int b0 = 0; b0 < B; b0 += nb) {
+    const int k = (B - b0 < nb) ? B - b0 : nb;
+    c->bk.sync(); c->wbc.feedback_gather(c->mpc.d, B, b0, k, stg, stg_u);
+    if (gain) c->bk.to_host(gain + (size_t)b0 * nm * 900, stg, (size_t)k * nm * 900 * 8);
+    if (uff) c->bk.to_host(uff + (size_t)b0 * nm * 30, stg_u, (size_t)k * nm * 30 * 8);
+  }
+  c->bk.sync(); hipFree(stg);
+  return c->hipstate();
+}
 int qmhip_wbc_reset(qmhip_ctx* c) { QM_GUARD(c); if (!c) return QMHIP_ERR_ARG; hipSetDevice(c->device); c->bk.cur = c->bk.stream_b; c->wbc.reset(); c->bk.cur = c->bk.stream; return c->hipstate(); }   // ordered with the WBC launches
 // The control-tick path (WbcBase::update on the ros_control thread, QMController.cpp:145-147).  Everything it enqueues goes to the WBC stream and the host waits for
 // THAT stream only: inputs staged in pinned memory -> asynchronous copies -> qm_wbc_kernel -> asynchronous copy of [out | qp_status] -> one stream synchronisation.
@@ -541,9 +576,11 @@ int qmhip_sim_get_state(qmhip_ctx* c, int B, double* q, double* v, double* time,
 int qmhip_closed_loop_sim(qmhip_ctx* c, int B, int n_ticks, double period, int n_substeps, int mpc_every, double horizon, double arm_kp, double arm_kd) { QM_GUARD(c); QM_NEED_MPC(c);
   if (!c || B <= 0 || B > c->max_batch || n_ticks <= 0 || !(period > 0) || n_substeps < 1 || mpc_every < 1 || !(horizon > 0)) { if (c) c->fail("qmhip_closed_loop_sim: bad argument"); return QMHIP_ERR_ARG; }
   if (!c->sim.s.Bmax) { c->fail("qmhip_closed_loop_sim: qmhip_sim_reset has not been called"); return QMHIP_ERR_STATE; }
+  const bool feedback = c->st[ST_FEEDBACK_POLICY] != 0.0;      // sqp.useFeedbackPolicy: the ticks evaluate the SQP's linear controller at the estimated state
+  if (feedback && c->mpc.solver != 0 && c->mpc.solver != 2) { c->fail("qmhip_closed_loop_sim: ST_FEEDBACK_POLICY = 1 needs a multiple-shooting solver slot (ST_SOLVER 0 / 2): the discrete iLQR (1) and the interior-point method (3) hand out no feedback policy"); return QMHIP_ERR_ARG; }
   hipSetDevice(c->device); c->bk.sync();
   qm_closed_loop_sim_ticks(c->bk, c->mpc, c->wbc, c->sim, c->sim_ticks, B, n_ticks, period, n_substeps, mpc_every, horizon, arm_kp, arm_kd, c->sqp_iterations(),
-                           [&]() { if (c->front_B == B) c->gait_schedule(B, horizon); });
+                           [&]() { if (c->front_B == B) c->gait_schedule(B, horizon); }, feedback);
   c->lastB = B; c->have_solution = true;
   return c->hipstate();
 }
@@ -551,6 +588,8 @@ int qmhip_closed_loop_sim(qmhip_ctx* c, int B, int n_ticks, double period, int n
 int qmhip_closed_loop_sim_pipelined(qmhip_ctx* c, int B, int n_ticks, double period, int n_substeps, int mpc_every, double horizon, double arm_kp, double arm_kd) { QM_GUARD(c); QM_NEED_MPC(c);
   if (!c || B <= 0 || B > c->max_batch || n_ticks <= 0 || !(period > 0) || n_substeps < 1 || mpc_every < 1 || !(horizon > 0)) { if (c) c->fail("qmhip_closed_loop_sim_pipelined: bad argument"); return QMHIP_ERR_ARG; }
   if (!c->sim.s.Bmax) { c->fail("qmhip_closed_loop_sim_pipelined: qmhip_sim_reset has not been called"); return QMHIP_ERR_STATE; }
+  // the pipelined ticks evaluate a PUBLISHED COPY of the policy while the next solve rewrites the stage records the gains live in; the copy holds the primal solution only
+  if (c->st[ST_FEEDBACK_POLICY] != 0.0) { c->fail("qmhip_closed_loop_sim_pipelined: ST_FEEDBACK_POLICY = 1 is not supported by the pipelined loop (the published policy carries no gains); use qmhip_closed_loop_sim or set it to 0"); return QMHIP_ERR_ARG; }
   if (n_ticks % mpc_every || c->sim_ticks % mpc_every) { c->fail("qmhip_closed_loop_sim_pipelined: n_ticks and the tick counter must be multiples of mpc_every"); return QMHIP_ERR_ARG; }
   hipSetDevice(c->device); c->bk.sync();
   qm_closed_loop_sim_pipelined(c->bk, c->mpc, c->wbc, c->sim, c->sim_ticks, B, n_ticks, period, n_substeps, mpc_every, horizon, arm_kp, arm_kd, c->sqp_iterations(),
