@@ -244,6 +244,43 @@ int qmhip_step_collect(qmhip_ctx* ctx, int B, qmhip_step_record* rec /*[B]*/,
                        double* out_t /*[B][max_nodes]*/, int32_t* out_event, int32_t* out_mode, double* out_x /*[B][max_nodes][30]*/, double* out_u);
 int qmhip_step_in_flight(const qmhip_ctx* ctx);   /* 0, 1 or 2 */
 
+/* ---- streamed controller tick for a plant on the host: QMController::update (qm_controllers/src/QMController.cpp:128-175) as a service — the measured state of B robots
+ *      in, their hybrid joint commands out, once per tick, the MPC on every mpc_every-th tick, the controller's state resident between ticks.  For a caller that owns the
+ *      plant (a batched simulator, hardware, the reference's QMHWSim) and has what the reference's estimator returns: measuredRbdState_ (55 doubles, the layout of
+ *      qmhip_wbc_step) and the contact flags.  Nothing is estimated here.
+ *      tick_reset = QMController::starting for a batch: zeroed observation (previous yaw 0), nothing commanded yet, stop flags cleared, tick counter 0; the episode starts cold
+ *        like qmhip_sim_reset (previous solution dropped) and the WBC's inputLast_ is zeroed (qmhip_wbc_reset).  controller: 0 qm::QMController, 1 qm::QMMpcController (as
+ *        qmhip_sim_set_controller); arm_kp / arm_kd: the arm gains of updateControlLaw.  References and schedule are the resident ones (qmhip_mpc_upload /
+ *        qmhip_mpc_update_references / the device gait front-end), exactly as for qmhip_step_submit.
+ *      tick_submit = one update, enqueued, nothing waited for:
+ *        1. observation: computeCentroidalStateFromRbdModel(rbd_meas) at time[b] (QMController.cpp:202-244), the yaw unwrapped against the instance's previous observation:
+ *           yaw + 2 pi k, k = nearbyint((yawLast - yaw) / 2 pi) — the reference's yawLast + shortest_angular_distance(yawLast, yaw) up to rounding; a yaw that does not
+ *           wrap passes unchanged, bit for bit.  Measured mode 8 LF + 4 RF + 2 LH + RH of contact[b] (-1 when contact is NULL).
+ *        2. on tick 0, mpc_every, 2 mpc_every ... since tick_reset: the MPC call of qmhip_closed_loop_sim on that observation (gait front-end refresh when it is active for
+ *           this batch, warm-started, sqp.sqpIteration iterations; cold when no solution of this batch exists).
+ *        3. the policy at the observation time: feed-forward, or with ST_FEEDBACK_POLICY = 1 the SQP's linear controller at the observed state (solver slots 1 / 3 with the
+ *           slot set: QMHIP_ERR_ARG).
+ *        4. the WBC on rbd_meas (hierarchy of `controller`); on tick 0 inputLast_ is primed with the planned input, as qmhip_closed_loop_sim does.
+ *        5. SafetyChecker::checkOrientation (SafetyChecker.h:25-32): roll state[11] outside +-pi/2 (strictly) sets safety = 1 in this tick's record — the tick still issues its
+ *           command, as the reference does (QMController.cpp:159-165) — and a STICKY stop flag for the instance: from the next tick on its record repeats the held command
+ *           with stopped = 1 and its controller state (held command, arm hold / publication times, previous yaw) is frozen; x_obs, x_des, u_des and wbc_out of a stopped
+ *           instance are still computed and reported, not used.  The rest of the batch is unaffected; tick_reset clears the flag.
+ *        6. updateControlLaw (QMController.cpp:177-190 / 431-445) into the instance's HELD command: under controller 0 the legs keep their held values (zeros after a reset)
+ *           until time > 10; under controller 1 the arm's held position starts at the measured arm pose of tick 0 and is re-published when more than 1/100 s have passed.
+ *        7. one struct qmhip_tick_record per instance — 2048 bytes, qmhip_layout.h —, packed on the device, one copy to pinned host memory, one event.
+ *      tick_collect waits for that event only and copies the records out.  Driven with the plant's own state and time, the pair reproduces qmhip_closed_loop_sim bit for bit
+ *      (tests/test_gpu_tick.py).  Trajectories are not part of the record: qmhip_mpc_download reads them.
+ *      observe: step 1 alone for host states, stateless (no unwrapping) — the centroidal state qmhip_mpc_set_initial / qmhip_step_submit want.
+ *      Depth is ONE.  QMHIP_ERR_STATE: a second tick_submit before the collect; tick_submit while a qmhip_step_submit is in flight and the other way round; tick_collect with
+ *      nothing in flight; a tick before tick_reset; a tick without an MPC call after the solution was dropped (upload, reset, solver switch); a WBC-only context.
+ *      QMHIP_ERR_ARG: B other than tick_reset's (or > max_batch), NULL time / rbd_meas / rec, mpc_every < 1, controller other than 0 / 1, horizon or period <= 0.
+ *      qmhip_policy_eval_feedback / qmhip_mpc_download_feedback return QMHIP_ERR_STATE while a tick is in flight. */
+int qmhip_tick_reset(qmhip_ctx* ctx, int B, int controller, double arm_kp, double arm_kd, int mpc_every);
+int qmhip_tick_submit(qmhip_ctx* ctx, int B, const double* time /*[B]*/, const double* rbd_meas /*[B][55]*/, const int32_t* contact /*[B][4] LF RF LH RH, or NULL*/,
+                      double horizon, double period);
+int qmhip_tick_collect(qmhip_ctx* ctx, int B, qmhip_tick_record* rec /*[B]*/);
+int qmhip_observe(qmhip_ctx* ctx, int B, const double* rbd /*[B][55]*/, double* x /*[B][30]*/);
+
 /* ---- batched rigid-body plant: stands where Gazebo + qm_gazebo::QMHWSim stand in the reference.
  *      sim_set_command = HybridJointHandle::setCommand as QMController::updateControlLaw issues it (qm_controllers/src/QMController.cpp:177-190):
  *        per joint posDes, velDes, kp, kd, ff in the reference's joint order (LF, LH, RF, RH, arm).
@@ -269,6 +306,8 @@ int qmhip_sim_reset(qmhip_ctx* ctx, int B, const double* q /*[B][24]*/, const do
 int qmhip_sim_set_command(qmhip_ctx* ctx, int B, const double* pos_des /*[B][18]*/, const double* vel_des, const double* kp, const double* kd, const double* ff);
 int qmhip_sim_step(qmhip_ctx* ctx, int B, double period, int n_substeps, double* rbd /*[B][55]*/, int32_t* contact /*[B][4]*/);
 int qmhip_sim_get_state(qmhip_ctx* ctx, int B, double* q, double* v, double* time, double* force /*[B][12]*/, int32_t* status /*[B]*/);
+/*      sim_get_rbd: rbd / contact of the plant's CURRENT state (what the last sim_step or sim_reset left) without stepping; either may be null */
+int qmhip_sim_get_rbd(qmhip_ctx* ctx, int B, double* rbd /*[B][55]*/, int32_t* contact /*[B][4]*/);
 /*      closed_loop_sim: n_ticks of the whole controller around the plant, device resident — QMController::update + mpcThread_
  *        (qm_controllers/src/QMController.cpp:128-175, 202-244, 315-332): state estimate = the plant's state ("ground truth" estimator,
  *        currentObservation_.state = computeCentroidalStateFromRbdModel), an MPC call on that observation every mpc_every ticks (warm-started SQP; the

@@ -178,4 +178,29 @@ typedef struct qmhip_step_record {
   int32_t mode, mpc_status, n_nodes, qp_status[3], reserved[2];
 } qmhip_step_record;
 
+/* record of one controller tick of one instance as qmhip_tick_collect hands it over (qmhip.h, "streamed controller tick"): a fixed 2048 bytes, packed on the device by
+   qm_tick_pack_kernel (csrc/kernels/k_tick.h).  QM_TICK_* are offsets in DOUBLES of the f64 part, QM_TICK_I_* indices of the int32 words behind it */
+#define QM_TICK_CMD     0    /* [90] held hybrid joint command: posDes, velDes, kp, kd, ff x 18 (the order qmhip_sim_set_command takes) */
+#define QM_TICK_XOBS    90   /* [30] the tick's observation (centroidal state, yaw unwrapped)             */
+#define QM_TICK_XDES    120  /* [30] policy state at the observation time                                 */
+#define QM_TICK_UDES    150  /* [30] policy input at the observation time                                 */
+#define QM_TICK_WBC     180  /* [54] WBC output [vdot(24), F(12), tau(18)]                                */
+#define QM_TICK_PERF    234  /* [10] perf of qmhip_mpc_download on a tick that ran the MPC, zeros otherwise */
+#define QM_TICK_DOUBLES 244
+#define QM_TICK_I_MODE    0  /* planned contact mode at the observation time                              */
+#define QM_TICK_I_MEAS    1  /* measured mode 8 LF + 4 RF + 2 LH + RH of the contact flags; -1 without    */
+#define QM_TICK_I_STATUS  2  /* MPC status word of the last MPC call, as qmhip_mpc_download reports it    */
+#define QM_TICK_I_NODES   3  /* number of nodes of the instance's grid (last MPC call)                    */
+#define QM_TICK_I_QP      4  /* [3] WBC status per priority level                                         */
+#define QM_TICK_I_SAFETY  7  /* 1: SafetyChecker::checkOrientation failed on THIS tick's observation      */
+#define QM_TICK_I_STOPPED 8  /* 1: the instance was stopped by an earlier tick: cmd is the held command   */
+#define QM_TICK_I_MPCRAN  9  /* 1: this tick ran the MPC                                                  */
+#define QM_TICK_I_TICK    10 /* tick index since qmhip_tick_reset                                         */
+#define QM_TICK_INTS      24 /* 11 .. 23 reserved (0)                                                     */
+#define QM_TICK_BYTES 2048
+typedef struct qmhip_tick_record {
+  double cmd[90], x_obs[30], x_des[30], u_des[30], wbc_out[54], perf[10];
+  int32_t mode, mode_meas, mpc_status, n_nodes, qp_status[3], safety, stopped, mpc_ran, tick, reserved[13];
+} qmhip_tick_record;
+
 #endif

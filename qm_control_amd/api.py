@@ -26,12 +26,16 @@ EXPORTS = ["qmhip_create", "qmhip_create_from_blobs", "qmhip_create_wbc_context"
            "qmhip_gait_set_templates", "qmhip_gait_reset", "qmhip_gait_insert_template", "qmhip_gait_update_resident", "qmhip_gait_download", "qmhip_schedule_download",
            "qmhip_target_reset", "qmhip_target_from_command", "qmhip_target_download",
            "qmhip_step_submit", "qmhip_step_collect", "qmhip_step_in_flight",
+           "qmhip_tick_reset", "qmhip_tick_submit", "qmhip_tick_collect", "qmhip_observe", "qmhip_sim_get_rbd",
            "qmhip_sim_set_params", "qmhip_sim_set_controller", "qmhip_sim_reset", "qmhip_sim_set_command", "qmhip_sim_step", "qmhip_sim_get_state", "qmhip_closed_loop_sim", "qmhip_closed_loop_sim_pipelined"]
 
 # struct qmhip_step_record (include/qmhip_layout.h) as a numpy structured dtype: one 1024-byte record per instance and control step
 STEP_WBC, STEP_TRAJ = 1, 2
 STEP_RECORD = np.dtype({"names": [f[0] for f in L.STEP_RECORD_FIELDS], "formats": [f[1] if f[2] == 1 else (f[1], (f[2],)) for f in L.STEP_RECORD_FIELDS],
                         "offsets": [f[3] for f in L.STEP_RECORD_FIELDS], "itemsize": L.QM_STEP_BYTES})
+# struct qmhip_tick_record: one 2048-byte record per instance and controller tick (QMController below)
+TICK_RECORD = np.dtype({"names": [f[0] for f in L.TICK_RECORD_FIELDS], "formats": [f[1] if f[2] == 1 else (f[1], (f[2],)) for f in L.TICK_RECORD_FIELDS],
+                        "offsets": [f[3] for f in L.TICK_RECORD_FIELDS], "itemsize": L.QM_TICK_BYTES})
 
 
 class QmhipError(RuntimeError):
@@ -136,6 +140,13 @@ class QMInterface:
         mb = self.model_blob
         return dict(robotMass=mb[L.MB_ROBOTMASS], centroidalInertiaNominal=mb[L.MB_INOM:L.MB_INOM + 9].reshape(3, 3).copy(), comToBasePositionNominal=mb[L.MB_RNOM:L.MB_RNOM + 3].copy(),
                     qPinocchioNominal=np.concatenate([np.zeros(6), mb[L.MB_QNOM:L.MB_QNOM + 18]]), stateDim=30, inputDim=30, generalizedCoordinatesNum=24, actuatedDofNum=18, numThreeDofContacts=4)
+
+    def observe(self, rbd):
+        """computeCentroidalStateFromRbdModel of measured rbd states [B][55] -> centroidal states [B][30] (qmhip_observe; stateless: the yaw is not unwrapped)"""
+        rbd = _f(rbd); B = rbd.shape[0]; assert rbd.shape == (B, 55)
+        x = np.zeros((B, 30))
+        self._check(self.lib.qmhip_observe(self.h, B, _p(rbd), _p(x)), "qmhip_observe")
+        return x
 
     def set_gain(self, name, value):
         """one field of the reference's dynamic_reconfigure config qm_wbc::WbcWeightConfig by NAME (WbcBase::dynamicCallback, WbcBase.cpp:69-116); False for a field
@@ -399,10 +410,47 @@ class QMHWSim:
         fn = self.lib.qmhip_closed_loop_sim_pipelined if pipelined else self.lib.qmhip_closed_loop_sim     # pipelined: the MPC beside the ticks, one period of latency
         self.itf._check(fn(self.itf.h, self.B, int(n_ticks), C.c_double(period), int(n_substeps), int(mpc_every), C.c_double(horizon), C.c_double(arm_kp), C.c_double(arm_kd)), "qmhip_closed_loop_sim")
 
+    def rbd(self):
+        """(rbd [B][55], contact [B][4]) of the plant's current state, without stepping (qmhip_sim_get_rbd)"""
+        B = self.B; rbd = np.zeros((B, 55)); contact = np.zeros((B, 4), np.int32)
+        self.itf._check(self.lib.qmhip_sim_get_rbd(self.itf.h, B, _p(rbd), _pi(contact)), "qmhip_sim_get_rbd")
+        return rbd, contact
+
     def state(self):
         B = self.B; q = np.zeros((B, 24)); v = np.zeros((B, 24)); t = np.zeros(B); f = np.zeros((B, 12)); st = np.zeros(B, np.int32)
         self.itf._check(self.lib.qmhip_sim_get_state(self.itf.h, B, _p(q), _p(v), _p(t), _p(f), _pi(st)), "qmhip_sim_get_state")
         return dict(q=q, v=v, time=t, force=f, status=st)
+
+
+class QMController:
+    """qm::QMController::update as a service for a plant on the host (qmhip_tick_reset / _submit / _collect): measured rbd states in, hybrid joint commands out, once
+    per tick, the MPC on every mpc_every-th tick, the controller's state on the device in between.  controller: 0 qm::QMController, 1 qm::QMMpcController; arm gains
+    default to the reference's dynamic-reconfigure defaults.  References and schedule: SqpMpc.set_problem / update_references or the device GaitSchedule, before starting()."""
+
+    def __init__(self, interface, batch, controller=0, arm_kp=0.0, arm_kd=0.5, mpc_every=5):
+        self.itf = interface; self.lib = interface.lib
+        self.B = int(batch); self.controller = int(controller); self.arm_kp = float(arm_kp); self.arm_kd = float(arm_kd); self.mpc_every = int(mpc_every)
+
+    def starting(self):
+        """QMController::starting: zeroed observation, nothing commanded, stop flags cleared, the next tick is tick 0 and solves cold"""
+        self.itf._check(self.lib.qmhip_tick_reset(self.itf.h, self.B, self.controller, C.c_double(self.arm_kp), C.c_double(self.arm_kd), self.mpc_every), "qmhip_tick_reset")
+
+    def update_submit(self, time, rbd, contact=None, *, horizon, period):
+        """one tick, enqueued and not waited for; time [B] (or a scalar), rbd [B][55], contact [B][4] (LF RF LH RH) or None"""
+        B = self.B; t = _f(np.broadcast_to(time, (B,))); rbd = _f(rbd, (B, 55))
+        ct = None if contact is None else np.ascontiguousarray(contact, dtype=np.int32)
+        assert ct is None or ct.shape == (B, 4)
+        self.itf._check(self.lib.qmhip_tick_submit(self.itf.h, B, _p(t), _p(rbd), _pi(ct), C.c_double(horizon), C.c_double(period)), "qmhip_tick_submit")
+
+    def update_collect(self):
+        """the tick in flight: records [B] of dtype TICK_RECORD (cmd = posDes, velDes, kp, kd, ff x 18, the order QMHWSim.setCommand takes)"""
+        rec = np.zeros(self.B, TICK_RECORD)
+        self.itf._check(self.lib.qmhip_tick_collect(self.itf.h, self.B, rec.ctypes.data_as(C.c_void_p)), "qmhip_tick_collect")
+        return rec
+
+    def update(self, time, rbd, contact=None, *, horizon, period):
+        self.update_submit(time, rbd, contact, horizon=horizon, period=period)
+        return self.update_collect()
 
 
 GAIT_MAX_PHASES, GAIT_EVENT_SLOTS = 16, 256

@@ -18,6 +18,7 @@
 #include "qm_front_pipeline.h"
 #include "qm_hoqp_pipeline.h"
 #include "qm_io_pipeline.h"
+#include "qm_tick_pipeline.h"
 
 static thread_local std::string g_create_error;      // per calling thread: qmhip_last_error(NULL) is the error of THIS thread's last failed create
 
@@ -46,7 +47,7 @@ struct HipBackend {
     const void* p = (const void*)k;
     if (p == (const void*)qm_grid_kernel || p == (const void*)qm_grid_nodes_kernel || p == (const void*)qm_save_grid_kernel || p == (const void*)qm_advance_kernel) return "grid"; if (p == (const void*)qm_lq_kernel || p == (const void*)qm_lq_dbg_kernel || p == (const void*)qm_lq_ipm_kernel) return "lq"; if (p == (const void*)qm_lq_m18_kernel) return "lq_m18"; if (p == (const void*)qm_lq_kin_kernel) return "lq_kin"; if (p == (const void*)qm_riccati_kernel || p == (const void*)qm_riccati_prof_kernel) return "riccati";
     if (p == (const void*)qm_ls_eval_kernel || p == (const void*)qm_ls_eval_dense_kernel || p == (const void*)qm_ls_eval_ipm_kernel) return "ls_eval";
-    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel) return "rollout"; if (p == (const void*)qm_sim_kernel) return "sim"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_policy_fb_kernel) return "policy_fb"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io";
+    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel) return "rollout"; if (p == (const void*)qm_sim_kernel) return "sim"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_policy_fb_kernel) return "policy_fb"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io"; if (p == (const void*)qm_tick_state_kernel || p == (const void*)qm_tick_pack_kernel) return "tick";
     return "ls_misc";
   }
   template <class K, class A> void launch(K kernel, int grid, int block, size_t lds, const A& args) {
@@ -97,6 +98,7 @@ struct HipBackend {
     if (wbc) { check(hipEventRecord(ev_io_b, stream_b), "hipEventRecord"); check(hipStreamWaitEvent(stream_c, ev_io_b, 0), "hipStreamWaitEvent"); }
     check(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToHost, stream_c), "D2H"); check(hipEventRecord((hipEvent_t)done, stream_c), "hipEventRecord");
   }
+  void copy_back(void* d, const void* s, size_t n, void* done) { check(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToHost, stream), "D2H"); check(hipEventRecord((hipEvent_t)done, stream), "hipEventRecord"); }      // streamed controller tick (qm_tick_pipeline.h): depth one, so the record travels on the stream that produced it
   void io_wait(void* done) { check(hipEventSynchronize((hipEvent_t)done), "hipEventSynchronize"); }
   // wait for a host-visible word a kernel already launched on `cur` overwrites (anything but `pending`): a BOUNDED spin — a stream synchronisation costs 10-30 us of
   // wake-up latency, which matters for a line-search trial of a few tens of microseconds, but a solve must not hold a host core beside the ros_control thread for its
@@ -121,14 +123,14 @@ struct HipBackend {
 struct qmhip_ctx {
   int device = 0, max_batch = 0, max_nodes = 0, max_ref = 0, max_ev = 0;
   double mb[MB_SIZE], st[ST_SIZE];
-  HipBackend bk; QmMpcPipeline<HipBackend> mpc; QmWbcPipeline<HipBackend> wbc; QmFrontPipeline<HipBackend> front; QmSimPipeline<HipBackend> sim; QmHoqpPipeline<HipBackend> hoqp; QmIoPipeline<HipBackend> io;
+  HipBackend bk; QmMpcPipeline<HipBackend> mpc; QmWbcPipeline<HipBackend> wbc; QmFrontPipeline<HipBackend> front; QmSimPipeline<HipBackend> sim; QmHoqpPipeline<HipBackend> hoqp; QmIoPipeline<HipBackend> io; QmTickPipeline<HipBackend> tick;
   std::recursive_mutex mu;      // serialises the entry points of this context
   bool wbc_only = false;        // created by qmhip_create_wbc_context: carries the model + the WBC buffers, no horizon buffers
   void* dl_dev = nullptr; void* dl_pin = nullptr; size_t dl_cap = 0;      // staging of qmhip_mpc_download (device transpose buffer + its pinned host mirror), allocated on first use
   char* tick_pin = nullptr;     // pinned host staging of the control-tick path (qmhip_wbc_step): [inputs of max_batch instances | outputs]
   std::string error; int lastB = 0; bool have_solution = false; int front_B = 0; long sim_ticks = 0;
   hipEvent_t ev_meas = nullptr; bool meas_pending = false;      // streamed step I/O: "the synthetic measured state of the last submitted step has read x0" (the next submit's copy of x0 waits for it on the device)
-  qmhip_ctx() : mpc(bk), wbc(bk), front(bk), sim(bk), hoqp(bk), io(bk) {}
+  qmhip_ctx() : mpc(bk), wbc(bk), front(bk), sim(bk), hoqp(bk), io(bk), tick(bk) {}
   void fail(const std::string& m) { error = m; }
   // getModeSchedule on the device GaitSchedule -> the solver's schedule buffers; from here on its sticky status speaks for the schedule of this batch (until the host supplies one)
   void gait_schedule(int B, double horizon) { front.gait_schedule(mpc.d, B, horizon); mpc.front_status = front.f.gs_status; mpc.front_B = B; }
@@ -250,7 +252,7 @@ int qmhip_create_wbc_context(const qmhip_ctx* c, int max_batch, qmhip_ctx** out)
   return create_common(c->mb, c->st, c->device, max_batch, 3, 1, 1, out, true);      // same model / settings values, own device copies, own streams: nothing mutable is shared
 }
 void qmhip_destroy(qmhip_ctx* c) {
-  if (!c) return; hipSetDevice(c->device); c->bk.sync(); if (c->bk.stream_c) hipStreamSynchronize(c->bk.stream_c); c->io.release(); if (c->ev_meas) hipEventDestroy(c->ev_meas); if (c->bk.ev_io_a) { hipEventDestroy(c->bk.ev_io_a); hipEventDestroy(c->bk.ev_io_b); } if (c->dl_dev) hipFree(c->dl_dev); if (c->dl_pin) hipHostFree(c->dl_pin); if (c->tick_pin) hipHostFree(c->tick_pin); c->mpc.release(); c->wbc.release(); c->front.release(); c->sim.release(); c->hoqp.release();
+  if (!c) return; hipSetDevice(c->device); c->bk.sync(); if (c->bk.stream_c) hipStreamSynchronize(c->bk.stream_c); c->io.release(); c->tick.release(); if (c->ev_meas) hipEventDestroy(c->ev_meas); if (c->bk.ev_io_a) { hipEventDestroy(c->bk.ev_io_a); hipEventDestroy(c->bk.ev_io_b); } if (c->dl_dev) hipFree(c->dl_dev); if (c->dl_pin) hipHostFree(c->dl_pin); if (c->tick_pin) hipHostFree(c->tick_pin); c->mpc.release(); c->wbc.release(); c->front.release(); c->sim.release(); c->hoqp.release();
   for (auto e : c->bk.pool) hipEventDestroy(e); if (c->bk.ev_order) hipEventDestroy(c->bk.ev_order); hipEventDestroy(c->bk.ev_in); hipEventDestroy(c->bk.ev_wbc); hipStreamDestroy(c->bk.stream); hipStreamDestroy(c->bk.stream_b); if (c->bk.stream_c) hipStreamDestroy(c->bk.stream_c); delete c;
 }
 // the text is copied under the context lock into a per-thread buffer: the pointer stays valid (until this THREAD's next qmhip_last_error) even if another thread's
@@ -416,6 +418,7 @@ int qmhip_policy_eval(qmhip_ctx* c, int B, const double* t, double* xd, double* 
 static int feedback_ready(qmhip_ctx* c, int B, const char* fn) {
   if (c->mpc.solver != 0 && c->mpc.solver != 2) { c->fail(std::string(fn) + ": the feedback policy exists for the multiple-shooting solver slots only (ST_SOLVER 0 / 2), not for the discrete iLQR (1) or the interior-point method (3)"); return QMHIP_ERR_ARG; }
   if (c->io.in_flight > 0) { c->fail(std::string(fn) + ": a qmhip_step_submit is in flight (qmhip_step_collect it first: its solve rewrites the stage records the gains are read from)"); return QMHIP_ERR_STATE; }
+  if (c->tick.in_flight > 0) { c->fail(std::string(fn) + ": a qmhip_tick_submit is in flight (qmhip_tick_collect it first)"); return QMHIP_ERR_STATE; }
   if (!c->have_solution) { c->fail(std::string(fn) + ": no policy received yet (no solve on this context since its creation, the last upload, reset or solver switch)"); return QMHIP_ERR_STATE; }
   if (B != c->mpc.solved_B) { c->fail(std::string(fn) + ": B differs from the batch size of the last solve"); return QMHIP_ERR_STATE; }
   return QMHIP_OK;
@@ -503,6 +506,7 @@ int qmhip_step_submit(qmhip_ctx* c, int B, const double* t0, const double* x0, c
   if (B <= 0 || B > c->max_batch || B != c->lastB || !t0 || !x0 || !(horizon > 0) || !(period > 0) || (flags & ~(unsigned)(QMHIP_STEP_WBC | QMHIP_STEP_TRAJ))) {
     c->fail("qmhip_step_submit: bad argument (B == batch of the last qmhip_mpc_upload, t0 / x0 not null, horizon > 0, period > 0, flags of QMHIP_STEP_*)"); return QMHIP_ERR_ARG; }
   if (c->io.in_flight >= 2) { c->fail("qmhip_step_submit: two steps are in flight already (qmhip_step_collect the oldest first)"); return QMHIP_ERR_STATE; }
+  if (c->tick.in_flight > 0) { c->fail("qmhip_step_submit: a qmhip_tick_submit is in flight (qmhip_tick_collect it first)"); return QMHIP_ERR_STATE; }
   hipSetDevice(c->device); HipBackend& bk = c->bk; const bool wbc = (flags & QMHIP_STEP_WBC) != 0, traj = (flags & QMHIP_STEP_TRAJ) != 0;
   if (!c->io.Bmax) { HIP_TRY(c, hipStreamCreate(&bk.stream_c)); HIP_TRY(c, hipEventCreateWithFlags(&c->ev_meas, hipEventDisableTiming)); c->io.allocate(c->max_batch); }      // first use: a context that never streams has the two streams it always had
   QmIoSlot& s = c->io.next(); bk.cur = bk.stream;
@@ -528,6 +532,47 @@ int qmhip_step_collect(qmhip_ctx* c, int B, qmhip_step_record* rec, double* ot, 
   return c->hipstate();
 }
 int qmhip_step_in_flight(const qmhip_ctx* c) { QM_GUARD(c); return c ? c->io.in_flight : 0; }
+
+// ---- streamed controller tick for a plant on the host (include/qmhip.h): measured rbd state in, hybrid joint command out ----
+// tick_submit enqueues one QMController::update for the batch on the MPC stream — the stream qmhip_closed_loop_sim runs its ticks on, with the same launches
+// (qm_tick_pipeline.h) — and returns; tick_collect waits for the one event behind the record's copy.
+int qmhip_tick_reset(qmhip_ctx* c, int B, int controller, double arm_kp, double arm_kd, int mpc_every) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c) return QMHIP_ERR_ARG;
+  if (B <= 0 || B > c->max_batch || (controller != 0 && controller != 1) || mpc_every < 1) { c->fail("qmhip_tick_reset: bad argument (0 < B <= max_batch, controller 0 / 1, mpc_every >= 1)"); return QMHIP_ERR_ARG; }
+  if (c->tick.in_flight > 0 || c->io.in_flight > 0) { c->fail("qmhip_tick_reset: a tick or a step is in flight (collect it first)"); return QMHIP_ERR_STATE; }
+  hipSetDevice(c->device); c->bk.sync(); c->bk.cur = c->bk.stream; c->tick.allocate(c->max_batch);
+  c->tick.reset(B, controller, arm_kp, arm_kd, mpc_every); c->wbc.reset();      // (on the MPC stream: the ticks' WBC launches run there)
+  c->mpc.solved_B = 0; c->have_solution = false;      // a new episode starts cold, like qmhip_sim_reset
+  return c->hipstate();
+}
+int qmhip_tick_submit(qmhip_ctx* c, int B, const double* time, const double* rbd_meas, const int32_t* contact, double horizon, double period) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c) return QMHIP_ERR_ARG;
+  if (c->tick.B == 0) { c->fail("qmhip_tick_submit: qmhip_tick_reset has not been called"); return QMHIP_ERR_STATE; }
+  if (B != c->tick.B || !time || !rbd_meas || !(horizon > 0) || !(period > 0)) { c->fail("qmhip_tick_submit: bad argument (B == batch of qmhip_tick_reset, time / rbd_meas not null, horizon > 0, period > 0)"); return QMHIP_ERR_ARG; }
+  if (c->tick.in_flight > 0) { c->fail("qmhip_tick_submit: a tick is in flight already (qmhip_tick_collect it first)"); return QMHIP_ERR_STATE; }
+  if (c->io.in_flight > 0) { c->fail("qmhip_tick_submit: a qmhip_step_submit is in flight (qmhip_step_collect it first)"); return QMHIP_ERR_STATE; }
+  const bool feedback = c->st[ST_FEEDBACK_POLICY] != 0.0;
+  if (feedback && c->mpc.solver != 0 && c->mpc.solver != 2) { c->fail("qmhip_tick_submit: ST_FEEDBACK_POLICY = 1 needs a multiple-shooting solver slot (ST_SOLVER 0 / 2): the discrete iLQR (1) and the interior-point method (3) hand out no feedback policy"); return QMHIP_ERR_ARG; }
+  if (!c->tick.mpc_tick() && (!c->have_solution || c->mpc.solved_B != B)) { c->fail("qmhip_tick_submit: no policy of this batch to evaluate on a tick without an MPC call (dropped by an upload, reset or solver switch since the last MPC tick)"); return QMHIP_ERR_STATE; }
+  hipSetDevice(c->device); c->bk.cur = c->bk.stream; c->bk.wbc_inputs_next();      // behind a WBC another entry point left on the WBC stream: the tick rewrites its inputs
+  const bool ran = c->tick.mpc_tick();
+  c->tick.submit(c->mpc, c->wbc, time, rbd_meas, (const int*)contact, horizon, period, c->sqp_iterations(), [&]() { if (c->front_B == B) c->gait_schedule(B, horizon); }, feedback, c->st[ST_RICCATI_STRICT] != 0.0);
+  if (ran) { c->lastB = B; c->have_solution = true; }
+  return c->hipstate();
+}
+int qmhip_tick_collect(qmhip_ctx* c, int B, qmhip_tick_record* rec) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c) return QMHIP_ERR_ARG;
+  if (c->tick.in_flight == 0) { c->fail("qmhip_tick_collect: no tick in flight"); return QMHIP_ERR_STATE; }
+  if (B != c->tick.B || !rec) { c->fail("qmhip_tick_collect: bad argument (B == batch of the tick in flight, rec not null)"); return QMHIP_ERR_ARG; }
+  hipSetDevice(c->device); c->tick.collect(rec);
+  return c->hipstate();
+}
+int qmhip_observe(qmhip_ctx* c, int B, const double* rbd, double* x) { QM_GUARD(c);
+  if (!c || B <= 0 || B > c->max_batch || !rbd || !x) { if (c) c->fail("qmhip_observe: bad argument"); return QMHIP_ERR_ARG; }
+  if (c->tick.in_flight > 0) { c->fail("qmhip_observe: a qmhip_tick_submit is in flight (it shares the tick's staging; qmhip_tick_collect it first)"); return QMHIP_ERR_STATE; }
+  hipSetDevice(c->device); c->bk.cur = c->bk.stream; c->tick.allocate(c->max_batch); c->tick.observe_host(c->mpc.d, B, rbd, x);
+  return c->hipstate();
+}
 
 // ---- batched rigid-body plant (QMHWSim.cpp:60-116) ----
 int qmhip_sim_set_params(qmhip_ctx* c, const double* p, int n) { QM_GUARD(c); QM_NEED_MPC(c);
@@ -567,6 +612,14 @@ int qmhip_sim_get_state(qmhip_ctx* c, int B, double* q, double* v, double* time,
   hipSetDevice(c->device);
   if (q) c->bk.to_host(q, c->sim.s.q, (size_t)B * 24 * 8); if (v) c->bk.to_host(v, c->sim.s.v, (size_t)B * 24 * 8); if (time) c->bk.to_host(time, c->sim.s.time, (size_t)B * 8);
   if (force) c->bk.to_host(force, c->sim.s.force, (size_t)B * 12 * 8); if (status) c->bk.to_host(status, c->sim.s.status, (size_t)B * 4);
+  return c->hipstate();
+}
+// the estimator-layout state / contact flags of the plant's CURRENT state (what the last qmhip_sim_step or qmhip_sim_reset left), without stepping
+int qmhip_sim_get_rbd(qmhip_ctx* c, int B, double* rbd, int32_t* contact) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c || B <= 0 || B > c->max_batch) { if (c) c->fail("qmhip_sim_get_rbd: bad argument"); return QMHIP_ERR_ARG; }
+  if (!c->sim.s.Bmax) { c->fail("qmhip_sim_get_rbd: qmhip_sim_reset has not been called"); return QMHIP_ERR_STATE; }
+  hipSetDevice(c->device);
+  if (rbd) c->bk.to_host(rbd, c->sim.s.rbd, (size_t)B * QM_NRBD * 8); if (contact) c->bk.to_host(contact, c->sim.s.contact, (size_t)B * 4 * 4);
   return c->hipstate();
 }
 

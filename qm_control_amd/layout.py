@@ -21,3 +21,12 @@ STEP_RECORD_FIELDS = [("x_des", "<f8", 30, 8 * QM_STEP_XDES), ("u_des", "<f8", 3
                       ("mode", "<i4", 1, 8 * QM_STEP_DOUBLES + 4 * QM_STEP_I_MODE), ("mpc_status", "<i4", 1, 8 * QM_STEP_DOUBLES + 4 * QM_STEP_I_STATUS),
                       ("n_nodes", "<i4", 1, 8 * QM_STEP_DOUBLES + 4 * QM_STEP_I_NODES), ("qp_status", "<i4", 3, 8 * QM_STEP_DOUBLES + 4 * QM_STEP_I_QP),
                       ("reserved", "<i4", 2, 8 * QM_STEP_DOUBLES + 4 * (QM_STEP_I_QP + 3))]
+
+# struct qmhip_tick_record (include/qmhip_layout.h), same form, from the QM_TICK_* defines
+_TI = 8 * QM_TICK_DOUBLES
+TICK_RECORD_FIELDS = [("cmd", "<f8", 90, 8 * QM_TICK_CMD), ("x_obs", "<f8", 30, 8 * QM_TICK_XOBS), ("x_des", "<f8", 30, 8 * QM_TICK_XDES), ("u_des", "<f8", 30, 8 * QM_TICK_UDES),
+                      ("wbc_out", "<f8", 54, 8 * QM_TICK_WBC), ("perf", "<f8", 10, 8 * QM_TICK_PERF),
+                      ("mode", "<i4", 1, _TI + 4 * QM_TICK_I_MODE), ("mode_meas", "<i4", 1, _TI + 4 * QM_TICK_I_MEAS), ("mpc_status", "<i4", 1, _TI + 4 * QM_TICK_I_STATUS),
+                      ("n_nodes", "<i4", 1, _TI + 4 * QM_TICK_I_NODES), ("qp_status", "<i4", 3, _TI + 4 * QM_TICK_I_QP), ("safety", "<i4", 1, _TI + 4 * QM_TICK_I_SAFETY),
+                      ("stopped", "<i4", 1, _TI + 4 * QM_TICK_I_STOPPED), ("mpc_ran", "<i4", 1, _TI + 4 * QM_TICK_I_MPCRAN), ("tick", "<i4", 1, _TI + 4 * QM_TICK_I_TICK),
+                      ("reserved", "<i4", 13, _TI + 4 * (QM_TICK_I_TICK + 1))]
