@@ -296,7 +296,7 @@ __device__ __forceinline__ void rw_stage(double* rec, int m, const double* nrec,
           E[I][J][r] = diag ? 1.0 : 0.0;
           if (diag && 16 * I + g + 4 * r >= m) Huu[I][I][r] = 1.0;
         }
-    auto recip = [](double d) { double x = __builtin_amdgcn_rcp(d); const double e = fma(-d, x, 1.0); return fma(fma(e, e, e), x, x); };   // 2^-24 estimate + one third-order step
+    // pivots: 1 / d by qm_frcp — the hardware estimate (no worse than 2^-24: tests/test_gpu_devprim.py) + one third-order step
     constexpr int NBLK = (MT == 1) ? 4 : 5;                              // m <= 16: rows 0..15;  m = 17, 18: one more block in the second tile row
     if (MT == 1) {
       // ---- ONE tile row (m <= 16), SOFTWARE PIPELINED over the blocks (round 6).  A wave issues in order, so the seven MFMAs of a block written back to back (as the general
@@ -314,10 +314,10 @@ __device__ __forceinline__ void rw_stage(double* rec, int m, const double* nrec,
 #define RW_PIV1(rb_) { const int q0_ = 4 * (rb_); D00 = qm_bcast(Hd[rb_], q0_); D01 = qm_bcast(Hd[rb_], q0_ + 1); D02 = qm_bcast(Hd[rb_], q0_ + 2); D03 = qm_bcast(Hd[rb_], q0_ + 3); \
         D11 = qm_bcast(Hd[rb_], 16 + q0_ + 1); D12 = qm_bcast(Hd[rb_], 16 + q0_ + 2); D13 = qm_bcast(Hd[rb_], 16 + q0_ + 3); \
         D22 = qm_bcast(Hd[rb_], 32 + q0_ + 2); D23 = qm_bcast(Hd[rb_], 32 + q0_ + 3); D33 = qm_bcast(Hd[rb_], 48 + q0_ + 3); \
-        d0 = D00; rd0 = (d0 > 0.0) ? recip(d0) : 0.0; }
-#define RW_PIV2() { l10 = D01 * rd0; l20 = D02 * rd0; l30 = D03 * rd0; d1 = fma(-l10, D01, D11); rd1 = (d1 > 0.0) ? recip(d1) : 0.0; }
-#define RW_PIV3() { t12 = fma(-l20, D01, D12); t13 = fma(-l30, D01, D13); l21 = t12 * rd1; l31 = t13 * rd1; d2 = fma(-l21, t12, fma(-l20, D02, D22)); rd2 = (d2 > 0.0) ? recip(d2) : 0.0; }
-#define RW_PIV4() { t23 = fma(-l31, t12, fma(-l30, D02, D23)); l32 = t23 * rd2; d3 = fma(-l32, t23, fma(-l31, t13, fma(-l30, D03, D33))); rd3 = (d3 > 0.0) ? recip(d3) : 0.0; }
+        d0 = D00; rd0 = (d0 > 0.0) ? qm_frcp(d0) : 0.0; }
+#define RW_PIV2() { l10 = D01 * rd0; l20 = D02 * rd0; l30 = D03 * rd0; d1 = fma(-l10, D01, D11); rd1 = (d1 > 0.0) ? qm_frcp(d1) : 0.0; }
+#define RW_PIV3() { t12 = fma(-l20, D01, D12); t13 = fma(-l30, D01, D13); l21 = t12 * rd1; l31 = t13 * rd1; d2 = fma(-l21, t12, fma(-l20, D02, D22)); rd2 = (d2 > 0.0) ? qm_frcp(d2) : 0.0; }
+#define RW_PIV4() { t23 = fma(-l31, t12, fma(-l30, D02, D23)); l32 = t23 * rd2; d3 = fma(-l32, t23, fma(-l31, t13, fma(-l30, D03, D33))); rd3 = (d3 > 0.0) ? qm_frcp(d3) : 0.0; }
 #define RW_PIV5() { chol_fail |= ((d0 > 0.0) & (d1 > 0.0) & (d2 > 0.0) & (d3 > 0.0)) ? 0 : failbit; \
         M10 = -l10; M21 = -l21; M32 = -l32; M20 = fma(l21, l10, -l20); M31 = fma(l32, l21, -l31); M30 = -(l30 + l31 * M10 + l32 * M20); }
       RW_PIV1(0) RW_PIV2() RW_PIV3() RW_PIV4() RW_PIV5()
@@ -366,15 +366,15 @@ __device__ __forceinline__ void rw_stage(double* rec, int m, const double* nrec,
       // dpotrf kernels under HPIPM's Riccati factorisation store a zero diagonal and a zero reciprocal there instead of failing: its multipliers l_ij, its row of the
       // trailing update (a2 below) and its rows of W and L⁻¹ (invr below) all vanish, i.e. that reduced input gets K_j = 0, k_j = 0 and the others are solved as if it were
       // not there.  The flag travels to the instance's status as the warning QM_MPC_WARN_PIVOT (ST_RICCATI_STRICT: as the failure -4).
-      const double d0 = D00, rd0 = (d0 > 0.0) ? recip(d0) : 0.0;
+      const double d0 = D00, rd0 = (d0 > 0.0) ? qm_frcp(d0) : 0.0;
       const double l10 = D01 * rd0, l20 = D02 * rd0, l30 = D03 * rd0;
-      const double d1 = fma(-l10, D01, D11), rd1 = (d1 > 0.0) ? recip(d1) : 0.0;
+      const double d1 = fma(-l10, D01, D11), rd1 = (d1 > 0.0) ? qm_frcp(d1) : 0.0;
       const double t12 = fma(-l20, D01, D12), t13 = fma(-l30, D01, D13);            // D12 − l20 l10 d0, D13 − l30 l10 d0
       const double l21 = t12 * rd1, l31 = t13 * rd1;
-      const double d2 = fma(-l21, t12, fma(-l20, D02, D22)), rd2 = (d2 > 0.0) ? recip(d2) : 0.0;
+      const double d2 = fma(-l21, t12, fma(-l20, D02, D22)), rd2 = (d2 > 0.0) ? qm_frcp(d2) : 0.0;
       const double t23 = fma(-l31, t12, fma(-l30, D02, D23));                        // D23 − l30 l20 d0 − l31 l21 d1
       const double l32 = t23 * rd2;
-      const double d3 = fma(-l32, t23, fma(-l31, t13, fma(-l30, D03, D33))), rd3 = (d3 > 0.0) ? recip(d3) : 0.0;
+      const double d3 = fma(-l32, t23, fma(-l31, t13, fma(-l30, D03, D33))), rd3 = (d3 > 0.0) ? qm_frcp(d3) : 0.0;
       if (!(d0 > 0.0) || !(d1 > 0.0) || !(d2 > 0.0) || !(d3 > 0.0)) chol_fail |= failbit;      // bit 0: on a stage of non-positive duration (benign, see above); bit 1: anywhere else or not a number -> hard failure
       // L~⁻¹ of the block (unit lower): its strictly lower entries
       const double M10 = -l10, M21 = -l21, M32 = -l32, M20 = fma(l21, l10, -l20), M31 = fma(l32, l21, -l31), M30 = -(l30 + l31 * M10 + l32 * M20);
@@ -406,8 +406,7 @@ __device__ __forceinline__ void rw_stage(double* rec, int m, const double* nrec,
     for (int I = 0; I < MT; ++I)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const double d = dsel[I][r]; double inv = __builtin_amdgcn_rsq(d);
-        inv = fma(0.5 * inv, fma(-d * inv, inv, 1.0), inv); inv = fma(0.5 * inv, fma(-d * inv, inv, 1.0), inv);
+        const double d = dsel[I][r]; const double inv = qm_rsqrt_n2(d);                  // estimate + two Newton steps (qm_dev_common.h)
         invr[I][r] = (d > 0.0) ? inv : 0.0;                            // a zeroed pivot: its rows of W and of L⁻¹ are zero
       }
     RWT(3)

@@ -108,25 +108,6 @@ __device__ __forceinline__ void dev_rot_error(const double* Rl, const double* Rr
   for (int i = 0; i < 3; ++i) err[i] = s * v[i];
 }
 
-// Householder scalars of a pivot column with squared norm nrm2 and pivot entry g: alpha = −sign(g)|x|, vk = g − alpha, b2 = 2 / (v·v).
-// v·v = 2 |x| (|x| + |g|), so b2 = (1/|x|) · 1/(|x| + |g|): one reciprocal square root and one reciprocal instead of a sqrt and a division.
-// This sits on the critical path of every Householder step of a lone wave (≈ 16 cycles per dependent f64 op), so the chain is kept short:
-// the hardware estimates (v_rsq_f64 / v_rcp_f64, 2^-24 on gfx950, measured) get ONE third-order correction each (error e³ ≈ 2^-70), and the
-// reciprocal's estimate is started from the ESTIMATED norm so that it overlaps the refinement of the rsqrt.  ok = false for a null column.
-__device__ __forceinline__ bool qm_house_scalars(double nrm2, double g, double& alpha, double& vk, double& b2) {
-  const bool ok = nrm2 > 0.0;
-  const double x = ok ? nrm2 : 1.0, ag = fabs(g);
-  const double y0 = __builtin_amdgcn_rsq(x);                        // 1/|x| (2^-24)
-  const double h = x * y0;                                          // |x| (2^-24)
-  const double q0 = __builtin_amdgcn_rcp(h + ag);                   // 1/(|x| + |g|) from the estimated norm: off the rsqrt's chain
-  const double e = fma(-h, y0, 1.0), t = fma(0.375, e, 0.5);        // 1/sqrt(x) = y0 (1 + e/2 + 3 e²/8 + O(e³)),  e = 1 − x y0²
-  const double r = fma(y0 * e, t, y0), nrm = fma(h * e, t, h);      // 1/|x| and |x| = x / |x|, both to ≈ 1 ulp
-  const double den = nrm + ag, e2 = fma(-den, q0, 1.0);
-  const double q = fma(fma(e2, e2, e2), q0, q0);                    // q0 (1 + e2 + e2²): 1/den to ≈ 1 ulp
-  alpha = g > 0.0 ? -nrm : nrm; vk = g - alpha; b2 = ok ? r * q : 0.0;
-  return ok;
-}
-
 // ---- wave-cooperative dense helpers ----
 // QR of [T; D]: T (n x (n+1), upper triangular with the rhs in column n, LDS, leading dim ldT) stacked on MRD dense rows held
 // by column in registers (lane j: d[0..MRD) = column j of D, lane n = its rhs, unused rows zero).  Step k only touches row k of T
@@ -257,19 +238,7 @@ __device__ __forceinline__ void wv_Z_times(const double* Zp, int n, const double
 #define WL_TQ_CO  (WL_G + WVLD * WTLD)            /* t, alpha, sigma, kappa, free part of t: 5 x 20 */
 #define WL_TQ_ROW (WL_TQ_CO + 100)                /* [18] the row to append (zero beyond n) */
 #define WL_TQ_H   (WL_TQ_ROW + 20)                /* [18] residual / Qᵀ gradient of the multiplier solve */
-// Givens pair with c a + s b = |(a, b)|, −s a + c b = 0 (identity for a null pair); the reciprocal root is the hardware estimate + one third-order correction (qm_house_scalars)
-__device__ __forceinline__ void qm_givens(double a, double b, double& c, double& s) {
-  const double h2 = fma(a, a, b * b); const bool ok = h2 > 0.0; const double x = ok ? h2 : 1.0;
-  const double y0 = __builtin_amdgcn_rsq(x), h = x * y0, e = fma(-h, y0, 1.0), r = fma(y0 * e, fma(0.375, e, 0.5), y0);
-  c = ok ? a * r : 1.0; s = ok ? b * r : 0.0;
-}
-// 1 / x from the hardware estimate (2^-24) and two Newton steps: ≈ 1 ulp, a third of the dependent chain of the IEEE division sequence
-__device__ __forceinline__ double qm_recip(double x) {
-  const double q0 = __builtin_amdgcn_rcp(x), e = fma(-x, q0, 1.0), q1 = fma(fma(e, e, e), q0, q0);
-  return fma(fma(-x, q1, 1.0), q1, q1);
-}
-// 1 / sqrt(x), x > 0 (same correction as qm_givens)
-__device__ __forceinline__ double qm_rsqrt(double x) { const double y0 = __builtin_amdgcn_rsq(x), h = x * y0, e = fma(-h, y0, 1.0); return fma(y0 * e, fma(0.375, e, 0.5), y0); }
+// (qm_house_scalars, qm_givens, qm_recip, qm_rsqrt — hardware estimate + correction steps — live in qm_dev_common.h; the estimates' error is asserted and recorded, and the primitives tested alone, by tests/test_emu_devprim.py, tests/test_gpu_devprim.py)
 // wv_solve_upper / wv_solve_lower for the factors of the TQ update: every lane loads its whole row UNCONDITIONALLY (`at` must be readable for every (lane row, i < MAXN)) and
 // masks in registers — a load under a wave-uniform condition becomes a scalar branch around each ds_read, which serialises them — and the diagonal is inverted by qm_recip
 template <int MAXN, class At>

@@ -140,7 +140,7 @@ __device__ __forceinline__ double barrier_val(double mu, double delta, double h)
   const bool in = h > delta; const double L = qm_log(in ? h : delta), t = (h - 2.0 * delta) * (1.0 / delta);   // 1/delta: one division per distinct delta after CSE
   return in ? -mu * L : mu * (-L + 0.5 * t * t - 0.5);
 }
-// 1 / x to ≈ 1 ulp: the hardware estimate (v_rcp_f64, 2^-24 on gfx950) + one third-order correction — 5 instructions against the ≈ 13 of an IEEE division
+// 1 / x to ≈ 1 ulp: the hardware estimate (v_rcp_f64, no worse than 2^-24 on gfx950: asserted and recorded by tests/test_gpu_devprim.py) + one third-order correction — 5 instructions against the ≈ 13 of an IEEE division
 // (v_div_scale x 2, v_rcp, four fused steps, v_div_fmas, v_div_fixup); for finite, normal x (every caller divides by a sum of squares or a barrier argument)
 __device__ __forceinline__ double qm_frcp(double x) { const double r = __builtin_amdgcn_rcp(x); const double e = fma(-x, r, 1.0); return fma(fma(e, e, e), r, r); }
 // first and second derivative of the relaxed log barrier: one reciprocal serves both (select the argument, then divide once)
@@ -151,6 +151,45 @@ __device__ __forceinline__ void barrier_d12(double mu, double delta, double h, d
 }
 __device__ __forceinline__ double barrier_d1(double mu, double delta, double h) { double a, b; barrier_d12(mu, delta, h, a, b); return a; }
 __device__ __forceinline__ double barrier_d2(double mu, double delta, double h) { double a, b; barrier_d12(mu, delta, h, a, b); return b; }
+
+// ---- pivot-chain scalars of the dense factorisations (WBC: Householder / Givens / triangular solves, K3: Cholesky pivots): hardware estimate + correction steps ----
+// Householder scalars of a pivot column with squared norm nrm2 and pivot entry g: alpha = −sign(g)|x|, vk = g − alpha, b2 = 2 / (v·v).
+// v·v = 2 |x| (|x| + |g|), so b2 = (1/|x|) · 1/(|x| + |g|): one reciprocal square root and one reciprocal instead of a sqrt and a division.
+// This sits on the critical path of every Householder step of a lone wave (≈ 16 cycles per dependent f64 op), so the chain is kept short:
+// the hardware estimates (v_rsq_f64 / v_rcp_f64, no worse than 2^-24 on gfx950: asserted and recorded by tests/test_gpu_devprim.py) get ONE third-order correction each (error e³ ≈ 2^-70), and the
+// reciprocal's estimate is started from the ESTIMATED norm so that it overlaps the refinement of the rsqrt.  ok = false for a null column.
+__device__ __forceinline__ bool qm_house_scalars(double nrm2, double g, double& alpha, double& vk, double& b2) {
+  const bool ok = nrm2 > 0.0;
+  const double x = ok ? nrm2 : 1.0, ag = fabs(g);
+  const double y0 = __builtin_amdgcn_rsq(x);                        // 1/|x| (2^-24)
+  const double h = x * y0;                                          // |x| (2^-24)
+  const double q0 = __builtin_amdgcn_rcp(h + ag);                   // 1/(|x| + |g|) from the estimated norm: off the rsqrt's chain
+  const double e = fma(-h, y0, 1.0), t = fma(0.375, e, 0.5);        // 1/sqrt(x) = y0 (1 + e/2 + 3 e²/8 + O(e³)),  e = 1 − x y0²
+  const double r = fma(y0 * e, t, y0), nrm = fma(h * e, t, h);      // 1/|x| and |x| = x / |x|, both to ≈ 1 ulp
+  const double den = nrm + ag, e2 = fma(-den, q0, 1.0);
+  const double q = fma(fma(e2, e2, e2), q0, q0);                    // q0 (1 + e2 + e2²): 1/den to ≈ 1 ulp
+  alpha = g > 0.0 ? -nrm : nrm; vk = g - alpha; b2 = ok ? r * q : 0.0;
+  return ok;
+}
+// Givens pair with c a + s b = |(a, b)|, −s a + c b = 0 (identity for a null pair); the reciprocal root is the hardware estimate + one third-order correction (qm_house_scalars)
+__device__ __forceinline__ void qm_givens(double a, double b, double& c, double& s) {
+  const double h2 = fma(a, a, b * b); const bool ok = h2 > 0.0; const double x = ok ? h2 : 1.0;
+  const double y0 = __builtin_amdgcn_rsq(x), h = x * y0, e = fma(-h, y0, 1.0), r = fma(y0 * e, fma(0.375, e, 0.5), y0);
+  c = ok ? a * r : 1.0; s = ok ? b * r : 0.0;
+}
+// 1 / x from the hardware estimate (2^-24) and two Newton steps: ≈ 1 ulp, a third of the dependent chain of the IEEE division sequence
+__device__ __forceinline__ double qm_recip(double x) {
+  const double q0 = __builtin_amdgcn_rcp(x), e = fma(-x, q0, 1.0), q1 = fma(fma(e, e, e), q0, q0);
+  return fma(fma(-x, q1, 1.0), q1, q1);
+}
+// 1 / sqrt(x), x > 0 (same correction as qm_givens)
+__device__ __forceinline__ double qm_rsqrt(double x) { const double y0 = __builtin_amdgcn_rsq(x), h = x * y0, e = fma(-h, y0, 1.0); return fma(y0 * e, fma(0.375, e, 0.5), y0); }
+// 1 / sqrt(d) from the hardware estimate and TWO Newton steps (K3's 1/L_jj = d_j^(-1/2), four independent chains per lane); the caller masks d <= 0
+__device__ __forceinline__ double qm_rsqrt_n2(double d) {
+  double inv = __builtin_amdgcn_rsq(d);
+  inv = fma(0.5 * inv, fma(-d * inv, inv, 1.0), inv); inv = fma(0.5 * inv, fma(-d * inv, inv, 1.0), inv);
+  return inv;
+}
 
 // contact index (LF,RF,LH,RH; ModelSettings.h:38) of leg chain c (joint order LF,LH,RF,RH; task.info:168-188)
 __device__ __forceinline__ int chain_to_contact(int c) { return (c == 1) ? 2 : (c == 2) ? 1 : c; }

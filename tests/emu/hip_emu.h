@@ -83,8 +83,12 @@ typedef double double4v __attribute__((ext_vector_type(4)));
 // global_load_lds: lane l's `size` bytes land at lds_base + size * l; the immediate offset `off` is added on BOTH sides
 #define __builtin_amdgcn_global_load_lds(g, l, size, off, aux) memcpy((char*)(l) + (off) + (size) * emu::cur().lane, (const char*)(g) + (off), (size))
 #define __ffsll(x) __builtin_ffsll(x)
+#ifndef __builtin_amdgcn_rsq      /* (tests/emu_prim models the estimates' error instead) */
 #define __builtin_amdgcn_rsq(x) (1.0 / std::sqrt((double)(x)))
+#endif
+#ifndef __builtin_amdgcn_rcp
 #define __builtin_amdgcn_rcp(x) (1.0 / (double)(x))
+#endif
 #define __builtin_amdgcn_fence(order, scope) ((void)0)
 #define __threadfence() ((void)0)
 #define __threadfence_system() ((void)0)
