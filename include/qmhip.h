@@ -182,6 +182,29 @@ int qmhip_policy_eval(qmhip_ctx* ctx, int B, const double* t, double* x_des /*[B
 int qmhip_policy_eval_feedback(qmhip_ctx* ctx, int B, const double* t /*[B]*/, const double* x /*[B][30] or NULL*/,
                                double* x_des /*[B][30]*/, double* u_des /*[B][30]*/, int32_t* mode /*[B]*/);
 int qmhip_mpc_download_feedback(qmhip_ctx* ctx, int B, double* gain /*[B][max_nodes][30][30]*/, double* uff /*[B][max_nodes][30]*/);
+/* ---- published feedback policy: the policy buffer MPC_MRT_Interface swaps in behind a mutex (updatePolicy + evaluatePolicy on the control thread, QMController.cpp:133-148,
+ *      while mpcThread_ computes the next solution, QMController.cpp:315-333).  A publication is a snapshot of the last solve — primal solution, grid, mode schedule and,
+ *      with ST_FEEDBACK_POLICY = 1, the gain data (PR_*, qmhip_layout.h) of the first `nodes` nodes of every instance — into the inactive one of two slots, which then
+ *      becomes the active one; it stays valid whatever the context solves next.
+ *      policy_set_publish_window: 0 (the default) = off: nothing is allocated and every other entry point behaves as without this block; 2 ... max_nodes allocates the two
+ *        slots (7.4 KB per instance and node of the window, plus two copies of the primal arrays) and drops earlier publications.  A tick looks at the two nodes bracketing
+ *        its time: the window must reach as far as the policy is evaluated behind t0 (one or two MPC periods).
+ *      policy_publish: snapshot of the last solve of a batch of B, in stream order behind it (also behind a qmhip_step_submit in flight) and in front of the next solve;
+ *        the sequence number advances by one.  QMHIP_ERR_STATE without a window or before any solve; QMHIP_ERR_ARG with ST_FEEDBACK_POLICY = 1 on solver slots 1 / 3
+ *        (the multiple-shooting slots only).  With ST_FEEDBACK_POLICY = 0 the publication carries the primal part only.
+ *      policy_eval_published: qmhip_policy_eval_feedback on the ACTIVE publication: u_des = the linear controller at (t[b], x[b]); x == NULL: the feed-forward policy.
+ *        covered[b] = 1 when both nodes bracketing t[b] lie inside the window (and the instance's grid); an instance that is not covered gets exactly the feed-forward
+ *        answer of qmhip_policy_eval — check `covered`.  *seq = the sequence number of the publication that was evaluated.  Runs on a stream of its own and takes a small
+ *        publication mutex, NOT the context lock: it may be called from a second thread while a solve, a streamed step or a loop runs on the context (evaluations are
+ *        serialised among themselves).  Ordering is by events on the device: an evaluation waits for its slot's publication, a publication into a slot for the last
+ *        evaluation enqueued on it.  QMHIP_ERR_STATE before the first publication, for a B other than the publication's, and for x != NULL on a publication without gains.
+ *      policy_published_info: sequence number of the active publication (0: none), the window, and per instance of the active publication's batch the number of ticks of
+ *        qmhip_closed_loop_sim_pipelined that were NOT covered since the last qmhip_sim_reset (any of the three may be NULL). */
+int qmhip_policy_set_publish_window(qmhip_ctx* ctx, int nodes);
+int qmhip_policy_publish(qmhip_ctx* ctx, int B);
+int qmhip_policy_eval_published(qmhip_ctx* ctx, int B, const double* t /*[B]*/, const double* x /*[B][30] or NULL*/, double* x_des /*[B][30]*/, double* u_des /*[B][30]*/,
+                                int32_t* mode /*[B]*/, int32_t* covered /*[B] or NULL*/, int64_t* seq /*out, or NULL*/);
+int qmhip_policy_published_info(qmhip_ctx* ctx, int64_t* seq, int32_t* window, int32_t* uncovered /*[B] or NULL*/);
 
 /* ---- WBC: replaces qm::WbcBase::update / HierarchicalWbc::update (qm_wbc/include/qm_wbc/WbcBase.h:31-32,
  *      qm_wbc/src/HierarchicalWbc.cpp:18-44; variant 1 = HierarchicalMpcWbc.cpp:18-34).
@@ -323,7 +346,10 @@ int qmhip_closed_loop_sim(qmhip_ctx* ctx, int B, int n_ticks, double period, int
  *        MPC call triggered at a tick observes the plant at that tick and computes on its own stream while the next mpc_every ticks run on the policy published
  *        before; its solution is published (MPC_MRT_Interface's policy buffer) when those ticks are done — a latency of one MPC period, deterministic instead of
  *        thread-timing dependent.  The first call after a reset is synchronous.  n_ticks and the tick counter must be multiples of mpc_every.
- *        The published policy is a copy of the primal solution and carries no gains: with ST_FEEDBACK_POLICY = 1 this loop returns QMHIP_ERR_ARG. */
+ *        Without a publish window the published policy is a copy of the primal solution and carries no gains: with ST_FEEDBACK_POLICY = 1 this loop then returns
+ *        QMHIP_ERR_ARG.  With a window (qmhip_policy_set_publish_window) and ST_FEEDBACK_POLICY = 1 the publication also carries the window's gains and every tick evaluates
+ *        the published linear controller at its estimated state (solver slots 0 / 2); a tick whose time runs past the window falls back to the feed-forward input for that
+ *        instance and is counted (qmhip_policy_published_info).  With ST_FEEDBACK_POLICY = 0 a window changes nothing in this loop. */
 int qmhip_closed_loop_sim_pipelined(qmhip_ctx* ctx, int B, int n_ticks, double period, int n_substeps, int mpc_every, double horizon, double arm_kp, double arm_kd);
 
 /* ---- instrumentation (ocs2 benchmark::RepeatedTimer analogue, QMController.cpp:145-147,321-323) ----

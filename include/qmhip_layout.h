@@ -147,6 +147,16 @@
    velocity boxes (rows 12 + 2k, 13 + 2k; 12 rows), friction cone of contact c (row 24 + c; inactive — slack 1, dual 0, no contribution — while the foot swings) */
 #define QM_NH 28
 
+/* published gain record (qmhip_policy_publish, "published feedback policy" in qmhip.h): the part of a node's stage record the feedback policy reads, copied by
+   qm_policy_publish_kernel (csrc/kernels/k_publish.h) into a double-buffered window of the first W nodes of every instance ([slot][instance][node][PR_SIZE]).  Offsets in
+   doubles; every field starts on a 16-byte boundary and the record is a whole number of 16-byte pieces.  A node without a record of its own holds zeros */
+#define PR_PP     0     /* [18][30] the Riccati gain K of the last SQP iteration                          */
+#define PR_PX     180   /* VIRTUAL base of Px [30][30]: only its rows 12..23 exist, at PR_PX + 360 = 540 ... 899 */
+#define PR_SWG    900   /* [4][6]   per contact: the 3 x 2 null-space block of a swing leg               */
+#define PR_MODEF  924   /* contact mode of the interval (as double); 925: 0                               */
+#define PR_SCAL   926   /* m, the reduced input dimension (as double); 927: 0                             */
+#define PR_SIZE   928   /* 7424 bytes                                                                     */
+
 /* contact-mode ids: 8*LF + 4*RF + 2*LH + 1*RH (ocs2_legged_robot MotionPhaseDefinition) */
 #define QM_MODE_STANCE 15
 #define QM_MODE_LF_RH  9

@@ -21,6 +21,7 @@ MB_SIZE, ST_SIZE = L.MB_SIZE, L.ST_SIZE
 EXPORTS = ["qmhip_create", "qmhip_create_from_blobs", "qmhip_create_wbc_context", "qmhip_destroy", "qmhip_last_error", "qmhip_parse_model", "qmhip_export_blobs",
            "qmhip_set_setting", "qmhip_wbc_gain_index", "qmhip_mpc_step", "qmhip_mpc_upload", "qmhip_mpc_solve_resident", "qmhip_mpc_set_initial", "qmhip_mpc_update_references", "qmhip_mpc_solve_resident_warm",
            "qmhip_mpc_advance_resident", "qmhip_closed_loop_resident", "qmhip_mpc_download", "qmhip_policy_eval", "qmhip_policy_eval_feedback", "qmhip_mpc_download_feedback",
+           "qmhip_policy_set_publish_window", "qmhip_policy_publish", "qmhip_policy_eval_published", "qmhip_policy_published_info",
            "qmhip_wbc_step", "qmhip_wbc_reset", "qmhip_hoqp_solve", "qmhip_control_step_resident", "qmhip_wbc_download", "qmhip_set_profiling",
            "qmhip_get_kernel_ms", "qmhip_reset_kernel_ms", "qmhip_synchronize", "qmhip_last_ls_trials", "qmhip_debug_read", "qmhip_debug_set", "qmhip_debug_get", "qmhip_microbench_fp64",
            "qmhip_gait_set_templates", "qmhip_gait_reset", "qmhip_gait_insert_template", "qmhip_gait_update_resident", "qmhip_gait_download", "qmhip_schedule_download",
@@ -161,6 +162,16 @@ class QMInterface:
         self._check(self.lib.qmhip_set_setting(self.h, C.c_int(index), C.c_double(value)), "qmhip_set_setting")
         self.settings_blob[index] = value
 
+    def set_publish_window(self, nodes):
+        """qmhip_policy_set_publish_window: 0 = off (nothing allocated); 2 ... max_nodes = two slots holding the first `nodes` nodes' gain data per instance"""
+        self._check(self.lib.qmhip_policy_set_publish_window(self.h, int(nodes)), "qmhip_policy_set_publish_window")
+
+    def published_info(self, B=0):
+        """(seq, window, uncovered [B]) of qmhip_policy_published_info; B: batch of the active publication (0: no counters)"""
+        seq = C.c_int64(0); w = C.c_int32(0); unc = np.zeros(max(int(B), 1), np.int32)
+        self._check(self.lib.qmhip_policy_published_info(self.h, C.byref(seq), C.byref(w), _pi(unc) if B else None), "qmhip_policy_published_info")
+        return seq.value, w.value, unc[:int(B)]
+
     # instrumentation
     def set_profiling(self, on):
         """False / True: spans around no / every launch; 2: only around the modelled kernels (lq, riccati, wbc)"""
@@ -299,6 +310,19 @@ class SqpMpc:
         self.itf._check(self.lib.qmhip_policy_eval_feedback(self.itf.h, self.B, _p(t), _p(xm), _p(xd), _p(u), _pi(mode)), "qmhip_policy_eval_feedback")
         return xd, u, mode
 
+    def publish_policy(self):
+        """MPC_MRT_Interface's policy hand-over (qmhip_policy_publish): snapshot of the last solve into the inactive publication slot, which becomes the active one; needs
+        QMInterface.set_publish_window"""
+        self.itf._check(self.lib.qmhip_policy_publish(self.itf.h, self.B), "qmhip_policy_publish")
+
+    def evaluate_published(self, t, x=None):
+        """updatePolicy + evaluatePolicy(t, x) on the ACTIVE publication (qmhip_policy_eval_published): safe beside a running solve, from another thread too.
+        Returns (x_des, u_des, mode, covered, seq); an instance with covered == 0 got the feed-forward input"""
+        B = self.B; t = _f(t, (B,)); xm = None if x is None else _f(x, (B, 30))
+        xd = np.zeros((B, 30)); u = np.zeros((B, 30)); mode = np.zeros(B, np.int32); cov = np.zeros(B, np.int32); seq = C.c_int64(0)
+        self.itf._check(self.lib.qmhip_policy_eval_published(self.itf.h, B, _p(t), _p(xm), _p(xd), _p(u), _pi(mode), _pi(cov), C.byref(seq)), "qmhip_policy_eval_published")
+        return xd, u, mode, cov, seq.value
+
     def feedback(self):
         """the linear controller of the last solve as ocs2::LinearController holds it (qmhip_mpc_download_feedback): (gain [B][max_nodes][30][30], uff [B][max_nodes][30]) on the
         time stamps of download()["t"]; nodes behind an instance's grid hold zeros"""
@@ -360,11 +384,13 @@ class QMHWSim:
     readSim (rbd state in the estimator's layout, contact flags)."""
     PARAMS = ("contact_stiffness", "contact_damping", "friction", "friction_speed_eps", "foot_radius", "delay", "saturate_effort")
 
-    def __init__(self, interface, robust_grid=False, feedback_policy=False, **params):
+    def __init__(self, interface, robust_grid=False, feedback_policy=False, publish_window=None, **params):
         """robust_grid: opt into the SQP time grid's robust minimum step (ST_GRID_DT_MIN = QM_GRID_DT_MIN_ROBUST, include/qmhip_layout.h) — for long fixed-rate loops whose
         1 ms observation raster can land within weakEpsilon of a gait event; the default keeps [upstream]'s 10 * limitEpsilon.
         feedback_policy: ST_FEEDBACK_POLICY = 1 (`sqp.useFeedbackPolicy true`): the ticks of closed_loop() evaluate the SQP's linear controller at the estimated state; False
-        leaves the context's setting as its task file / blob has it"""
+        leaves the context's setting as its task file / blob has it.
+        publish_window: nodes of the published gain window (QMInterface.set_publish_window) — with it closed_loop(pipelined=True) runs the feedback policy too; None leaves
+        the context's window as it is"""
         self.itf = interface
         self.lib = interface.lib
         self.B = 0
@@ -372,6 +398,8 @@ class QMHWSim:
             interface.set_setting(L.ST_GRID_DT_MIN, L.QM_GRID_DT_MIN_ROBUST)
         if feedback_policy:
             interface.set_setting(L.ST_FEEDBACK_POLICY, 1.0)
+        if publish_window is not None:
+            interface.set_publish_window(publish_window)
         if params:
             self.set_params(**params)
 

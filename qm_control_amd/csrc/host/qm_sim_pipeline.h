@@ -100,14 +100,26 @@ void qm_closed_loop_sim_ticks(BK& bk, QmMpcPipeline<BK>& mpc, QmWbcPipeline<BK>&
 // first call is synchronous (there is no policy yet).  n_ticks and the tick counter must be multiples of mpc_every.  BK::stream_select(s) makes stream s (0: MPC,
 // 1: ticks) the target of the following launches, BK::stream_order(a, b) orders everything launched so far on a before everything launched later on b; the
 // host emulator runs the same sequence on one queue (identical results: the data dependencies are the same).
-template <class BK, class PreMpc>
+// pub (a QmPublishPipeline<BK> with a window, qm_publish_pipeline.h; ST_FEEDBACK_POLICY = 1 — the caller checks both): the publication also snapshots the first nodes' gain
+// records, and every tick evaluates the published LINEAR controller at its estimated centroidal state, as the synchronous loop does on the live records.  Without it
+// (QmNoPublish) the loop is the feed-forward one, launch for launch
+struct QmNoPublish { static constexpr bool enabled = false; };
+template <class BK, class PreMpc, class Pub = QmNoPublish>
 void qm_closed_loop_sim_pipelined(BK& bk, QmMpcPipeline<BK>& mpc, QmWbcPipeline<BK>& wbc, QmSimPipeline<BK>& sim, long& sim_ticks, int B, int n_ticks, double period, int n_substeps,
-                                  int mpc_every, double horizon, double arm_kp, double arm_kd, int sqp_iters, PreMpc pre_mpc) {
+                                  int mpc_every, double horizon, double arm_kp, double arm_kd, int sqp_iters, PreMpc pre_mpc, Pub* pub = nullptr) {
   auto solve = [&]() { pre_mpc(); mpc.grid(B, horizon, true); for (int it = 0; it < sqp_iters; ++it) mpc.sqp_iteration(B, 14, it + 1 == sqp_iters); };
+  auto publish = [&]() {
+    if constexpr (Pub::enabled) { if (pub) { pub->publish(mpc.d, B, true); sim.s.p_valid = true; return; } }
+    sim.publish_policy(mpc.d);
+  };
+  auto policy = [&]() {
+    if constexpr (Pub::enabled) { if (pub) { sim.estimate(mpc.d, B); pub->tick_policy(wbc, B, sim.s.time, sim.s.x_est); return; } }
+    QmPolicyArgs pa = wbc.pargs(mpc.d, B, sim.s.time); pa.n_nodes = sim.s.p_n_nodes; pa.node_t = sim.s.p_node_t; pa.node_ev = sim.s.p_node_ev; pa.xs = sim.s.p_xs; pa.us = sim.s.p_us; pa.ev = sim.s.p_ev; pa.modes = sim.s.p_modes;
+    bk.launch(qm_policy_kernel, (B + 63) / 64, 64, 0, pa);
+  };
   auto ticks = [&]() {
     for (int k = 0; k < mpc_every; ++k) {
-      QmPolicyArgs pa = wbc.pargs(mpc.d, B, sim.s.time); pa.n_nodes = sim.s.p_n_nodes; pa.node_t = sim.s.p_node_t; pa.node_ev = sim.s.p_node_ev; pa.xs = sim.s.p_xs; pa.us = sim.s.p_us; pa.ev = sim.s.p_ev; pa.modes = sim.s.p_modes;
-      bk.launch(qm_policy_kernel, (B + 63) / 64, 64, 0, pa);
+      policy();
       if (sim_ticks == 0) bk.copy_dd(wbc.w.input_last, wbc.w.u_des, (size_t)B * 30 * 8);
       wbc.step(mpc.d, B, period, sim.controller == 1 ? 1 : 0, sim.s.rbd, sim.s.time);
       sim.command(B, wbc.w.x_des, wbc.w.u_des, wbc.w.out, arm_kp, arm_kd);
@@ -117,13 +129,15 @@ void qm_closed_loop_sim_pipelined(BK& bk, QmMpcPipeline<BK>& mpc, QmWbcPipeline<
   };
   for (int p = 0; p < n_ticks / mpc_every; ++p) {
     bk.stream_select(1); sim.observe(mpc.d, B); bk.stream_order(1, 0);
-    if (!sim.s.p_valid) {                       // no policy yet: solve first, then run the ticks of this period on it
+    bool have = sim.s.p_valid && sim.s.p_xs != nullptr;
+    if constexpr (Pub::enabled) { if (pub) { int k = -1; pub->book.info(nullptr, nullptr, &k, nullptr); have = sim.s.p_valid && k >= 0; } }      // (the two kinds of loop publish into buffers of their own)
+    if (!have) {                                // no policy yet: solve first, then run the ticks of this period on it
       bk.stream_select(0); solve(); bk.stream_order(0, 1);
-      bk.stream_select(1); sim.publish_policy(mpc.d); ticks();
+      bk.stream_select(1); publish(); ticks();
     } else {
       bk.stream_select(1); ticks();             // enqueued first: they run while the host waits inside the solve's line search
       bk.stream_select(0); solve(); bk.stream_order(0, 1);
-      bk.stream_select(1); sim.publish_policy(mpc.d);
+      bk.stream_select(1); publish();
     }
     bk.stream_order(1, 0);                      // the next solve must not overwrite the solution before it has been published
   }

@@ -19,6 +19,7 @@
 #include "qm_hoqp_pipeline.h"
 #include "qm_io_pipeline.h"
 #include "qm_tick_pipeline.h"
+#include "qm_publish_pipeline.h"
 
 static thread_local std::string g_create_error;      // per calling thread: qmhip_last_error(NULL) is the error of THIS thread's last failed create
 
@@ -47,7 +48,7 @@ struct HipBackend {
     const void* p = (const void*)k;
     if (p == (const void*)qm_grid_kernel || p == (const void*)qm_grid_nodes_kernel || p == (const void*)qm_save_grid_kernel || p == (const void*)qm_advance_kernel) return "grid"; if (p == (const void*)qm_lq_kernel || p == (const void*)qm_lq_dbg_kernel || p == (const void*)qm_lq_ipm_kernel) return "lq"; if (p == (const void*)qm_lq_m18_kernel) return "lq_m18"; if (p == (const void*)qm_lq_kin_kernel) return "lq_kin"; if (p == (const void*)qm_riccati_kernel || p == (const void*)qm_riccati_prof_kernel) return "riccati";
     if (p == (const void*)qm_ls_eval_kernel || p == (const void*)qm_ls_eval_dense_kernel || p == (const void*)qm_ls_eval_ipm_kernel) return "ls_eval";
-    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel) return "rollout"; if (p == (const void*)qm_sim_kernel) return "sim"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_policy_fb_kernel) return "policy_fb"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io"; if (p == (const void*)qm_tick_state_kernel || p == (const void*)qm_tick_pack_kernel) return "tick";
+    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel) return "rollout"; if (p == (const void*)qm_sim_kernel) return "sim"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_policy_fb_kernel || p == (const void*)qm_policy_fb_pub_kernel) return "policy_fb"; if (p == (const void*)qm_policy_publish_kernel) return "publish"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io"; if (p == (const void*)qm_tick_state_kernel || p == (const void*)qm_tick_pack_kernel) return "tick";
     return "ls_misc";
   }
   template <class K, class A> void launch(K kernel, int grid, int block, size_t lds, const A& args) {
@@ -99,6 +100,11 @@ struct HipBackend {
     check(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToHost, stream_c), "D2H"); check(hipEventRecord((hipEvent_t)done, stream_c), "hipEventRecord");
   }
   void copy_back(void* d, const void* s, size_t n, void* done) { check(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToHost, stream), "D2H"); check(hipEventRecord((hipEvent_t)done, stream), "hipEventRecord"); }      // streamed controller tick (qm_tick_pipeline.h): depth one, so the record travels on the stream that produced it
+  // published policy (qm_publish_pipeline.h): one event per slot and direction, on whichever stream is current
+  void* pub_event() { return io_event(); }
+  void pub_event_free(void* e) { io_event_free(e); }
+  void pub_wait(void* e) { check(hipStreamWaitEvent(cur, (hipEvent_t)e, 0), "hipStreamWaitEvent"); }
+  void pub_record(void* e) { check(hipEventRecord((hipEvent_t)e, cur), "hipEventRecord"); }
   void io_wait(void* done) { check(hipEventSynchronize((hipEvent_t)done), "hipEventSynchronize"); }
   // wait for a host-visible word a kernel already launched on `cur` overwrites (anything but `pending`): a BOUNDED spin — a stream synchronisation costs 10-30 us of
   // wake-up latency, which matters for a line-search trial of a few tens of microseconds, but a solve must not hold a host core beside the ros_control thread for its
@@ -123,14 +129,16 @@ struct HipBackend {
 struct qmhip_ctx {
   int device = 0, max_batch = 0, max_nodes = 0, max_ref = 0, max_ev = 0;
   double mb[MB_SIZE], st[ST_SIZE];
-  HipBackend bk; QmMpcPipeline<HipBackend> mpc; QmWbcPipeline<HipBackend> wbc; QmFrontPipeline<HipBackend> front; QmSimPipeline<HipBackend> sim; QmHoqpPipeline<HipBackend> hoqp; QmIoPipeline<HipBackend> io; QmTickPipeline<HipBackend> tick;
+  HipBackend bk; QmMpcPipeline<HipBackend> mpc; QmWbcPipeline<HipBackend> wbc; QmFrontPipeline<HipBackend> front; QmSimPipeline<HipBackend> sim; QmHoqpPipeline<HipBackend> hoqp; QmIoPipeline<HipBackend> io; QmTickPipeline<HipBackend> tick; QmPublishPipeline<HipBackend> pub;
+  // qmhip_policy_eval_published: a stream, staging and device buffers of its own, serialised among evaluators by eval_mu — an evaluation never takes `mu` below
+  std::mutex eval_mu; hipStream_t stream_p = nullptr; char* pe_pin = nullptr; char* pe_dev = nullptr;
   std::recursive_mutex mu;      // serialises the entry points of this context
   bool wbc_only = false;        // created by qmhip_create_wbc_context: carries the model + the WBC buffers, no horizon buffers
   void* dl_dev = nullptr; void* dl_pin = nullptr; size_t dl_cap = 0;      // staging of qmhip_mpc_download (device transpose buffer + its pinned host mirror), allocated on first use
   char* tick_pin = nullptr;     // pinned host staging of the control-tick path (qmhip_wbc_step): [inputs of max_batch instances | outputs]
   std::string error; int lastB = 0; bool have_solution = false; int front_B = 0; long sim_ticks = 0;
   hipEvent_t ev_meas = nullptr; bool meas_pending = false;      // streamed step I/O: "the synthetic measured state of the last submitted step has read x0" (the next submit's copy of x0 waits for it on the device)
-  qmhip_ctx() : mpc(bk), wbc(bk), front(bk), sim(bk), hoqp(bk), io(bk), tick(bk) {}
+  qmhip_ctx() : mpc(bk), wbc(bk), front(bk), sim(bk), hoqp(bk), io(bk), tick(bk), pub(bk) {}
   void fail(const std::string& m) { error = m; }
   // getModeSchedule on the device GaitSchedule -> the solver's schedule buffers; from here on its sticky status speaks for the schedule of this batch (until the host supplies one)
   void gait_schedule(int B, double horizon) { front.gait_schedule(mpc.d, B, horizon); mpc.front_status = front.f.gs_status; mpc.front_B = B; }
@@ -252,7 +260,7 @@ int qmhip_create_wbc_context(const qmhip_ctx* c, int max_batch, qmhip_ctx** out)
   return create_common(c->mb, c->st, c->device, max_batch, 3, 1, 1, out, true);      // same model / settings values, own device copies, own streams: nothing mutable is shared
 }
 void qmhip_destroy(qmhip_ctx* c) {
-  if (!c) return; hipSetDevice(c->device); c->bk.sync(); if (c->bk.stream_c) hipStreamSynchronize(c->bk.stream_c); c->io.release(); c->tick.release(); if (c->ev_meas) hipEventDestroy(c->ev_meas); if (c->bk.ev_io_a) { hipEventDestroy(c->bk.ev_io_a); hipEventDestroy(c->bk.ev_io_b); } if (c->dl_dev) hipFree(c->dl_dev); if (c->dl_pin) hipHostFree(c->dl_pin); if (c->tick_pin) hipHostFree(c->tick_pin); c->mpc.release(); c->wbc.release(); c->front.release(); c->sim.release(); c->hoqp.release();
+  if (!c) return; hipSetDevice(c->device); c->bk.sync(); if (c->bk.stream_c) hipStreamSynchronize(c->bk.stream_c); c->io.release(); c->tick.release(); if (c->stream_p) hipStreamSynchronize(c->stream_p); c->pub.release(); if (c->pe_pin) hipHostFree(c->pe_pin); if (c->pe_dev) hipFree(c->pe_dev); if (c->stream_p) hipStreamDestroy(c->stream_p); if (c->ev_meas) hipEventDestroy(c->ev_meas); if (c->bk.ev_io_a) { hipEventDestroy(c->bk.ev_io_a); hipEventDestroy(c->bk.ev_io_b); } if (c->dl_dev) hipFree(c->dl_dev); if (c->dl_pin) hipHostFree(c->dl_pin); if (c->tick_pin) hipHostFree(c->tick_pin); c->mpc.release(); c->wbc.release(); c->front.release(); c->sim.release(); c->hoqp.release();
   for (auto e : c->bk.pool) hipEventDestroy(e); if (c->bk.ev_order) hipEventDestroy(c->bk.ev_order); hipEventDestroy(c->bk.ev_in); hipEventDestroy(c->bk.ev_wbc); hipStreamDestroy(c->bk.stream); hipStreamDestroy(c->bk.stream_b); if (c->bk.stream_c) hipStreamDestroy(c->bk.stream_c); delete c;
 }
 // the text is copied under the context lock into a per-thread buffer: the pointer stays valid (until this THREAD's next qmhip_last_error) even if another thread's
@@ -448,6 +456,74 @@ int qmhip_mpc_download_feedback(qmhip_ctx* c, int B, double* gain, double* uff) 
   c->bk.sync(); hipFree(stg);
   return c->hipstate();
 }
+
+// ---- published feedback policy (include/qmhip.h): a double-buffered snapshot of the last solve — primal solution, grid, schedule and the first W nodes' gain records —
+// that stays valid while the next solve rewrites the stage records; evaluated on a stream of its own under the publication mutex, never the context lock ----
+static size_t pe_bytes(int B) { return (size_t)B * ((1 + 30 + 30 + 30) * 8 + 2 * 4); }      // [t | x | x_des | u_des | mode | covered]
+int qmhip_policy_set_publish_window(qmhip_ctx* c, int nodes) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c) return QMHIP_ERR_ARG;
+  if (nodes != 0 && (nodes < 2 || nodes > c->max_nodes)) { c->fail("qmhip_policy_set_publish_window: the window is 0 (off) or 2 ... max_nodes nodes"); return QMHIP_ERR_ARG; }
+  std::lock_guard<std::mutex> ev(c->eval_mu);      // no evaluation is under way, and none starts, while the slots are replaced
+  hipSetDevice(c->device); c->bk.sync(); if (c->stream_p) c->bk.check(hipStreamSynchronize(c->stream_p), "sync");
+  c->bk.cur = c->bk.stream; c->pub.set_window(c->mpc.d, nodes);
+  if (nodes && !c->stream_p) {
+    HIP_TRY(c, hipStreamCreate(&c->stream_p)); HIP_TRY(c, hipHostMalloc((void**)&c->pe_pin, pe_bytes(c->max_batch), hipHostMallocDefault)); HIP_TRY(c, hipMalloc((void**)&c->pe_dev, pe_bytes(c->max_batch)));
+  }
+  c->bk.sync(); return c->hipstate();
+}
+int qmhip_policy_publish(qmhip_ctx* c, int B) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c || B <= 0 || B > c->max_batch) { if (c) c->fail("qmhip_policy_publish: bad argument"); return QMHIP_ERR_ARG; }
+  if (c->pub.W == 0) { c->fail("qmhip_policy_publish: no publish window (qmhip_policy_set_publish_window has not been called, or with 0)"); return QMHIP_ERR_STATE; }
+  const bool gains = c->st[ST_FEEDBACK_POLICY] != 0.0;
+  if (gains && c->mpc.solver != 0 && c->mpc.solver != 2) { c->fail("qmhip_policy_publish: ST_FEEDBACK_POLICY = 1 needs a multiple-shooting solver slot (ST_SOLVER 0 / 2): the discrete iLQR (1) and the interior-point method (3) hand out no feedback policy"); return QMHIP_ERR_ARG; }
+  if (!c->have_solution || c->mpc.solved_B != B) { c->fail("qmhip_policy_publish: no policy received yet (no solve of this batch on this context since its creation, the last upload, reset or solver switch)"); return QMHIP_ERR_STATE; }
+  hipSetDevice(c->device); c->bk.cur = c->bk.stream;      // behind the solve (or the streamed step) that produced the solution, in front of the next one: the stream's order
+  if (c->pub.publish(c->mpc.d, B, gains) < 0) { c->fail("qmhip_policy_publish: no publish window"); return QMHIP_ERR_STATE; }
+  return c->hipstate();
+}
+int qmhip_policy_eval_published(qmhip_ctx* c, int B, const double* t, const double* x, double* xd, double* ud, int32_t* mode, int32_t* covered, int64_t* seq) {
+  if (!c) return QMHIP_ERR_ARG;
+  int rc = QMHIP_OK; std::string msg;
+  if (c->wbc_only) { rc = QMHIP_ERR_STATE; msg = "qmhip_policy_eval_published: not available on a WBC-only context (qmhip_create_wbc_context)"; }
+  else if (B <= 0 || B > c->max_batch || !t) { rc = QMHIP_ERR_ARG; msg = "qmhip_policy_eval_published: bad argument"; }
+  else {
+    std::lock_guard<std::mutex> ev(c->eval_mu);
+    auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && rc == QMHIP_OK) { rc = QMHIP_ERR_HIP; msg = std::string("qmhip_policy_eval_published: ") + what + ": " + hipGetErrorString(e); } };
+    QmPubBook::Eval tk;
+    if (!c->pub.book.begin_eval(tk)) { rc = QMHIP_ERR_STATE; msg = "qmhip_policy_eval_published: no policy published yet (qmhip_policy_set_publish_window, then qmhip_policy_publish after a solve)"; }
+    else if (B != tk.B) { c->pub.book.end_eval(tk, false); rc = QMHIP_ERR_STATE; msg = "qmhip_policy_eval_published: B differs from the batch size of the publication"; }
+    else if (x && !tk.gains) { c->pub.book.end_eval(tk, false); rc = QMHIP_ERR_STATE; msg = "qmhip_policy_eval_published: the active publication carries no gains (it was made with ST_FEEDBACK_POLICY = 0); pass x = NULL for its feed-forward policy"; }
+    else {
+      hip(hipSetDevice(c->device), "hipSetDevice");
+      char* h = c->pe_pin; char* d = c->pe_dev; const size_t o_x = (size_t)B * 8, o_xd = o_x + (size_t)B * 240, o_ud = o_xd + (size_t)B * 240, o_mode = o_ud + (size_t)B * 240, o_cov = o_mode + (size_t)B * 4;
+      memcpy(h, t, (size_t)B * 8); if (x) memcpy(h + o_x, x, (size_t)B * 240);
+      const QmPubSlot& s = c->pub.slot[tk.slot]; hipStream_t sp = c->stream_p;
+      hip(hipStreamWaitEvent(sp, (hipEvent_t)s.ev_pub, 0), "hipStreamWaitEvent");
+      hip(hipMemcpyAsync(d, h, x ? o_xd : o_x, hipMemcpyHostToDevice, sp), "H2D");
+      if (rc == QMHIP_OK) {
+        const QmPolicyFbPubArgs a = c->pub.eval_args(tk.slot, B, (const double*)d, x ? (const double*)(d + o_x) : nullptr, (double*)(d + o_xd), (double*)(d + o_ud), (int*)(d + o_mode), (int*)(d + o_cov), nullptr);
+        hipLaunchKernelGGL(qm_policy_fb_pub_kernel, dim3(B), dim3(64), 0, sp, a); hip(hipGetLastError(), "kernel launch");
+      }
+      hip(hipMemcpyAsync(h + o_xd, d + o_xd, pe_bytes(B) - o_xd, hipMemcpyDeviceToHost, sp), "D2H");
+      hip(hipEventRecord((hipEvent_t)s.ev_eval, sp), "hipEventRecord");
+      c->pub.book.end_eval(tk, true);      // enqueued: from here on a publication may go ahead (it is ordered behind this evaluation by the slot's event)
+      hip(hipStreamSynchronize(sp), "sync");
+      if (rc == QMHIP_OK) {
+        if (xd) memcpy(xd, h + o_xd, (size_t)B * 240); if (ud) memcpy(ud, h + o_ud, (size_t)B * 240); if (mode) memcpy(mode, h + o_mode, (size_t)B * 4); if (covered) memcpy(covered, h + o_cov, (size_t)B * 4);
+        if (seq) *seq = (int64_t)tk.seq;
+      }
+    }
+  }
+  if (rc != QMHIP_OK) { QM_GUARD(c); c->fail(msg); }      // (the context lock only for the error text, with nothing else held)
+  return rc;
+}
+int qmhip_policy_published_info(qmhip_ctx* c, int64_t* seq, int32_t* window, int32_t* uncovered) { QM_GUARD(c);
+  if (!c) return QMHIP_ERR_ARG;
+  long sq = 0; int w = 0, B = 0; c->pub.book.info(&sq, &w, nullptr, &B);
+  if (seq) *seq = (int64_t)sq; if (window) *window = w;
+  if (uncovered && B > 0) { hipSetDevice(c->device); c->bk.to_host(uncovered, c->pub.uncovered, (size_t)B * 4); }
+  return c->hipstate();
+}
 int qmhip_wbc_reset(qmhip_ctx* c) { QM_GUARD(c); if (!c) return QMHIP_ERR_ARG; hipSetDevice(c->device); c->bk.cur = c->bk.stream_b; c->wbc.reset(); c->bk.cur = c->bk.stream; return c->hipstate(); }   // ordered with the WBC launches
 // The control-tick path (WbcBase::update on the ros_control thread, QMController.cpp:145-147).  Everything it enqueues goes to the WBC stream and the host waits for
 // THAT stream only: inputs staged in pinned memory -> asynchronous copies -> qm_wbc_kernel -> asynchronous copy of [out | qp_status] -> one stream synchronisation.
@@ -588,7 +664,7 @@ int qmhip_sim_set_controller(qmhip_ctx* c, int controller) { QM_GUARD(c); QM_NEE
 }
 int qmhip_sim_reset(qmhip_ctx* c, int B, const double* q, const double* v, const double* time) { QM_GUARD(c); QM_NEED_MPC(c);
   if (!c || B <= 0 || B > c->max_batch || !q || !v || !time) { if (c) c->fail("qmhip_sim_reset: bad argument"); return QMHIP_ERR_ARG; }
-  hipSetDevice(c->device); c->sim.allocate(c->max_batch); c->sim.reset(B, q, v, time); c->sim_ticks = 0;
+  hipSetDevice(c->device); c->sim.allocate(c->max_batch); c->sim.reset(B, q, v, time); c->sim_ticks = 0; c->pub.reset_counters();
   c->mpc.solved_B = 0; c->have_solution = false;      // a new episode starts cold, like the reference after "Simulation reset" (no warm start from the previous episode's trajectory)
   c->sim.step(c->mpc.d.mb, B, 0.0, 0); return c->hipstate();   // rbd / contact of the reset state
 }
@@ -642,11 +718,14 @@ int qmhip_closed_loop_sim_pipelined(qmhip_ctx* c, int B, int n_ticks, double per
   if (!c || B <= 0 || B > c->max_batch || n_ticks <= 0 || !(period > 0) || n_substeps < 1 || mpc_every < 1 || !(horizon > 0)) { if (c) c->fail("qmhip_closed_loop_sim_pipelined: bad argument"); return QMHIP_ERR_ARG; }
   if (!c->sim.s.Bmax) { c->fail("qmhip_closed_loop_sim_pipelined: qmhip_sim_reset has not been called"); return QMHIP_ERR_STATE; }
   // the pipelined ticks evaluate a PUBLISHED COPY of the policy while the next solve rewrites the stage records the gains live in; the copy holds the primal solution only
-  if (c->st[ST_FEEDBACK_POLICY] != 0.0) { c->fail("qmhip_closed_loop_sim_pipelined: ST_FEEDBACK_POLICY = 1 is not supported by the pipelined loop (the published policy carries no gains); use qmhip_closed_loop_sim or set it to 0"); return QMHIP_ERR_ARG; }
+  // without a publish window (qmhip_policy_set_publish_window) that copy holds the primal solution only
+  const bool feedback = c->st[ST_FEEDBACK_POLICY] != 0.0;
+  if (feedback && c->pub.W == 0) { c->fail("qmhip_closed_loop_sim_pipelined: ST_FEEDBACK_POLICY = 1 is not supported by the pipelined loop without a publish window (the published policy carries no gains); call qmhip_policy_set_publish_window, use qmhip_closed_loop_sim or set it to 0"); return QMHIP_ERR_ARG; }
+  if (feedback && c->mpc.solver != 0 && c->mpc.solver != 2) { c->fail("qmhip_closed_loop_sim_pipelined: ST_FEEDBACK_POLICY = 1 needs a multiple-shooting solver slot (ST_SOLVER 0 / 2): the discrete iLQR (1) and the interior-point method (3) hand out no feedback policy"); return QMHIP_ERR_ARG; }
   if (n_ticks % mpc_every || c->sim_ticks % mpc_every) { c->fail("qmhip_closed_loop_sim_pipelined: n_ticks and the tick counter must be multiples of mpc_every"); return QMHIP_ERR_ARG; }
   hipSetDevice(c->device); c->bk.sync();
   qm_closed_loop_sim_pipelined(c->bk, c->mpc, c->wbc, c->sim, c->sim_ticks, B, n_ticks, period, n_substeps, mpc_every, horizon, arm_kp, arm_kd, c->sqp_iterations(),
-                               [&]() { if (c->front_B == B) c->gait_schedule(B, horizon); });
+                               [&]() { if (c->front_B == B) c->gait_schedule(B, horizon); }, feedback ? &c->pub : (QmPublishPipeline<HipBackend>*)nullptr);
   c->lastB = B; c->have_solution = true; c->bk.sync();
   return c->hipstate();
 }

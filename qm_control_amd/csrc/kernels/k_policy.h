@@ -85,6 +85,11 @@ __device__ __forceinline__ int qm_fb_source_node(const int* node_ev, int n, int 
 }
 // row r of Pu under contact mode md: its (at most two) non-zero entries sit in columns col, col + 1 with weights w1, w2.  Column order of K1b's projector: three force
 // components per stance foot, two null-space directions per swing leg, six arm joint velocities (contacts in the order LF RF LH RH)
+// (the record's fields are addressed through a view — QmFbView: the offsets of K, the virtual base of Px, the swing blocks, the mode and m — so that the same code reads
+// a stage record, QmFbStageView, and the compact published record of k_publish.h)
+template <int PP, int PX, int SWG, int MODEF, int SCAL> struct QmFbView { static constexpr int pp = PP, px = PX, swg = SWG, modef = MODEF, scal = SCAL; };
+typedef QmFbView<SR_PP, SR_PX, SR_SWG, SR_MODEF, SR_SCAL> QmFbStageView;
+template <class V = QmFbStageView>
 __device__ __forceinline__ void qm_fb_pu_row(const double* rec, int md, int r, int* col, double* w1, double* w2) {
   int nst = 0; for (int k = 0; k < 4; ++k) nst += mode_flag(md, k) ? 1 : 0;
   const int kk = (r < 12) ? r / 3 : ((r < 24) ? chain_to_contact((r - 12) / 3) : 0), r3 = (r < 12) ? r % 3 : ((r < 24) ? (r - 12) % 3 : r - 24);
@@ -92,20 +97,21 @@ __device__ __forceinline__ void qm_fb_pu_row(const double* rec, int md, int r, i
   const bool stf = mode_flag(md, kk);
   *col = (r < 12) ? 3 * before_st + r3 : ((r < 24) ? 3 * nst + 2 * before_sw : 3 * nst + 2 * (4 - nst) + r3);
   if (r < 12) { *w1 = stf ? 1.0 : 0.0; *w2 = 0.0; }
-  else if (r < 24) { const double s1 = rec[SR_SWG + 6 * kk + r3], s2 = rec[SR_SWG + 6 * kk + 3 + r3]; *w1 = stf ? 0.0 : s1; *w2 = stf ? 0.0 : s2; }
+  else if (r < 24) { const double s1 = rec[V::swg + 6 * kk + r3], s2 = rec[V::swg + 6 * kk + 3 + r3]; *w1 = stf ? 0.0 : s1; *w2 = stf ? 0.0 : s2; }
   else { *w1 = 1.0; *w2 = 0.0; }
 }
 // lane l (< 30): component l of K_full dx = Px dx + Pu (K dx) from one stage record; dxl = the lane's component of dx (0 in lanes >= 30).  One row of K and one of Px per lane
+template <class V = QmFbStageView>
 __device__ __forceinline__ double qm_fb_du(const double* rec, const double dxl, const int l) {
-  const int m = (int)rec[SR_SCAL], md = (int)rec[SR_MODEF];
+  const int m = (int)rec[V::scal], md = (int)rec[V::modef];
   const int r = (l < 30) ? l : 0; const bool hasPx = r >= 12 && r < 24, hasK = l < m; const int lr = hasK ? l : 0, pr = hasPx ? r : 12;
   double w[30], px[30];      // every record entry the lane needs is requested before the first dependent use
 #pragma unroll
-  for (int q = 0; q < 30; ++q) { w[q] = rec[SR_PP + lr * 30 + q]; px[q] = rec[SR_PX + pr * 30 + q]; }
+  for (int q = 0; q < 30; ++q) { w[q] = rec[V::pp + lr * 30 + q]; px[q] = rec[V::px + pr * 30 + q]; }
   double v = 0.0, s = 0.0;
 #pragma unroll
   for (int q = 0; q < 30; ++q) { const double d = qm_bcast(dxl, q); v += (hasK ? w[q] : 0.0) * d; s += (hasPx ? px[q] : 0.0) * d; }      // uniform control flow around the broadcasts
-  int col; double w1, w2; qm_fb_pu_row(rec, md, r, &col, &w1, &w2);
+  int col; double w1, w2; qm_fb_pu_row<V>(rec, md, r, &col, &w1, &w2);
   const double v1 = __shfl(v, col & 63, 64), v2 = __shfl(v, (col + 1) & 63, 64);      // (lanes >= m hold 0: a unit row whose column is m − 1 reads a zero beside it)
   return s + w1 * v1 + w2 * v2;
 }
