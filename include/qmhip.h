@@ -304,6 +304,26 @@ int qmhip_tick_submit(qmhip_ctx* ctx, int B, const double* time /*[B]*/, const d
 int qmhip_tick_collect(qmhip_ctx* ctx, int B, qmhip_tick_record* rec /*[B]*/);
 int qmhip_observe(qmhip_ctx* ctx, int B, const double* rbd /*[B][55]*/, double* x /*[B][30]*/);
 
+/* ---- planned task-space trajectories: the arithmetic of qm::QmVisualizer (qm_interface/src/visualization/qm_visualization.cpp:72-317) without its ROS messages —
+ *      where the feet, the base and the arm's end effector are along a plan, which forces act where, where the feet will land.  One 512-byte qmhip_plan_record
+ *      (include/qmhip_layout.h) per node: node time, mode and stance mask, base pose, the four foot positions / velocities / contact forces (contact order LF RF LH RH,
+ *      world frame), the end-effector pose and its error against the node's reference, the centre of pressure of the stance feet (cop[2] = their summed f_z; cop[0:2] = 0
+ *      when that sum is not positive) ([upstream getCenterOfPressureMarker, recalled]).
+ *      plan_task_space (publishOptimizedStateTrajectory, qm_visualization.cpp:90-189): the records of the primal solution of the LAST solve, [B][max_nodes]; records at
+ *        or behind num_nodes[b] are zero.  Works behind any solver slot.
+ *      plan_footholds (the "Future footholds" of qm_visualization.cpp:150-182): for every schedule event strictly inside the instance's grid (t_first < t_e < t_last) the
+ *        plan interpolated linearly at t_e and one qmhip_foothold per foot that is off before and on behind the event, ordered by (event, foot).  count[b] is the full
+ *        number of landings; only the first `cap` are written.
+ *      task_space_eval (publishDesiredTrajectory, qm_visualization.cpp:194-251: the target knots; publishObservation, qm_visualization.cpp:267-283: the observation): the
+ *        same record for R <= max_batch * max_nodes caller-supplied (state, input, mode) rows; u NULL = zero inputs, ee_ref NULL = no reference (ee_err = 0); time = 0.
+ *      All three run on the MPC stream behind whatever it holds and wait for that stream only; buffers are allocated by the first call, not by qmhip_create.
+ *      QMHIP_ERR_STATE: no solution (no solve since creation, the last upload, reset or solver switch), B other than the last solve's, a WBC-only context; nothing is
+ *      written then.  QMHIP_ERR_ARG: B or R out of range, NULL rec / x / mode / count, cap < 0, NULL out with cap > 0. */
+int qmhip_plan_task_space(qmhip_ctx* ctx, int B, qmhip_plan_record* rec /*[B][max_nodes]*/, int32_t* num_nodes /*[B] or NULL*/);
+int qmhip_plan_footholds(qmhip_ctx* ctx, int B, int cap, qmhip_foothold* out /*[B][cap]*/, int32_t* count /*[B]*/);
+int qmhip_task_space_eval(qmhip_ctx* ctx, int R, const double* x /*[R][30]*/, const double* u /*[R][30] or NULL*/, const int32_t* mode /*[R]*/,
+                          const double* ee_ref /*[R][7] pos + quat xyzw, or NULL*/, qmhip_plan_record* rec /*[R]*/);
+
 /* ---- batched rigid-body plant: stands where Gazebo + qm_gazebo::QMHWSim stand in the reference.
  *      sim_set_command = HybridJointHandle::setCommand as QMController::updateControlLaw issues it (qm_controllers/src/QMController.cpp:177-190):
  *        per joint posDes, velDes, kp, kd, ff in the reference's joint order (LF, LH, RF, RH, arm).
@@ -353,7 +373,7 @@ int qmhip_closed_loop_sim(qmhip_ctx* ctx, int B, int n_ticks, double period, int
 int qmhip_closed_loop_sim_pipelined(qmhip_ctx* ctx, int B, int n_ticks, double period, int n_substeps, int mpc_every, double horizon, double arm_kp, double arm_kd);
 
 /* ---- instrumentation (ocs2 benchmark::RepeatedTimer analogue, QMController.cpp:145-147,321-323) ----
- * per-kernel HIP-event timing on the stream each kernel runs on; names: "grid","lq_kin","lq","riccati","ls_eval","ls_misc","policy","wbc","sim".
+ * per-kernel HIP-event timing on the stream each kernel runs on; names: "grid","lq_kin","lq","riccati","ls_eval","ls_misc","policy","wbc","sim","plan_nodes","plan_states","plan_footholds".
  * enable: 0 off, 1 a span around every launch, 2 only around the three modelled kernels "lq","riccati","wbc", 3 only around "lq" — the dominant kernel, all the
  * bench's timed region carries (two event records cost about one launch) */
 int qmhip_set_profiling(qmhip_ctx* ctx, int enable);

@@ -213,4 +213,39 @@ typedef struct qmhip_tick_record {
   int32_t mode, mode_meas, mpc_status, n_nodes, qp_status[3], safety, stopped, mpc_ran, tick, reserved[13];
 } qmhip_tick_record;
 
+/* record of one node of a plan in task space as qmhip_plan_task_space / qmhip_task_space_eval hand it over (qmhip.h, "planned task-space trajectories"): 64 eight-byte
+   words, written on the device by the kernels of csrc/kernels/k_plan.h.  PT_* are offsets in 8-byte WORDS.  All vectors in the world frame; feet in CONTACT order
+   LF RF LH RH (the order of the input's force triples) */
+#define PT_TIME       0    /* node time (0 from qmhip_task_space_eval)                                   */
+#define PT_MODE       1    /* two int32: mode id of the node | contact_mask (bit i = foot i in stance)   */
+#define PT_BASE_POS   2    /* [3] x[6:9]                                                                 */
+#define PT_BASE_ZYX   5    /* [3] x[9:12]                                                                */
+#define PT_FOOT_POS   8    /* [4][3] foot frame positions                                                */
+#define PT_FOOT_VEL   20   /* [4][3] foot velocities as the zero- / normal-velocity constraints see them */
+#define PT_FOOT_FORCE 32   /* [4][3] u[3 i : 3 i + 3]                                                    */
+#define PT_EE_POS     44   /* [3] arm end-effector frame position                                        */
+#define PT_EE_QUAT    47   /* [4] its orientation, quaternion xyzw                                       */
+#define PT_EE_ERR     51   /* [6] EndEffectorConstraint's position / orientation error; zeros without a reference */
+#define PT_COP        57   /* [3] centre of pressure x, y over the stance feet; [2] = their summed f_z   */
+#define PT_SPARE      60   /* [4] zero                                                                   */
+#define QM_PLAN_WORDS 64
+#define QM_PLAN_BYTES 512
+typedef struct qmhip_plan_record {
+  double time;
+  int32_t mode, contact_mask;
+  double base_pos[3], base_zyx[3], foot_pos[4][3], foot_vel[4][3], foot_force[4][3], ee_pos[3], ee_quat[4], ee_err[6], cop[3], spare[4];
+} qmhip_plan_record;
+/* one landing of one foot inside the planned horizon (qmhip_plan_footholds): event = index into the instance's schedule, leg in contact order */
+#define QM_FOOTHOLD_BYTES 40
+typedef struct qmhip_foothold { double time; int32_t leg, event; double pos[3]; } qmhip_foothold;
+#ifdef __cplusplus
+#include <stddef.h>
+static_assert(sizeof(qmhip_plan_record) == QM_PLAN_BYTES && QM_PLAN_WORDS * 8 == QM_PLAN_BYTES, "qmhip_plan_record is 64 eight-byte words");
+static_assert(offsetof(qmhip_plan_record, mode) == 8 * PT_MODE && offsetof(qmhip_plan_record, contact_mask) == 8 * PT_MODE + 4 && offsetof(qmhip_plan_record, base_pos) == 8 * PT_BASE_POS &&
+              offsetof(qmhip_plan_record, base_zyx) == 8 * PT_BASE_ZYX && offsetof(qmhip_plan_record, foot_pos) == 8 * PT_FOOT_POS && offsetof(qmhip_plan_record, foot_vel) == 8 * PT_FOOT_VEL &&
+              offsetof(qmhip_plan_record, foot_force) == 8 * PT_FOOT_FORCE && offsetof(qmhip_plan_record, ee_pos) == 8 * PT_EE_POS && offsetof(qmhip_plan_record, ee_quat) == 8 * PT_EE_QUAT &&
+              offsetof(qmhip_plan_record, ee_err) == 8 * PT_EE_ERR && offsetof(qmhip_plan_record, cop) == 8 * PT_COP && offsetof(qmhip_plan_record, spare) == 8 * PT_SPARE, "PT_* are the word offsets of qmhip_plan_record");
+static_assert(sizeof(qmhip_foothold) == QM_FOOTHOLD_BYTES && offsetof(qmhip_foothold, leg) == 8 && offsetof(qmhip_foothold, event) == 12 && offsetof(qmhip_foothold, pos) == 16, "qmhip_foothold is 40 bytes");
+#endif
+
 #endif

@@ -27,6 +27,7 @@ EXPORTS = ["qmhip_create", "qmhip_create_from_blobs", "qmhip_create_wbc_context"
            "qmhip_gait_set_templates", "qmhip_gait_reset", "qmhip_gait_insert_template", "qmhip_gait_update_resident", "qmhip_gait_download", "qmhip_schedule_download",
            "qmhip_target_reset", "qmhip_target_from_command", "qmhip_target_download",
            "qmhip_step_submit", "qmhip_step_collect", "qmhip_step_in_flight",
+           "qmhip_plan_task_space", "qmhip_plan_footholds", "qmhip_task_space_eval",
            "qmhip_tick_reset", "qmhip_tick_submit", "qmhip_tick_collect", "qmhip_observe", "qmhip_sim_get_rbd",
            "qmhip_sim_set_params", "qmhip_sim_set_controller", "qmhip_sim_reset", "qmhip_sim_set_command", "qmhip_sim_step", "qmhip_sim_get_state", "qmhip_closed_loop_sim", "qmhip_closed_loop_sim_pipelined"]
 
@@ -37,6 +38,12 @@ STEP_RECORD = np.dtype({"names": [f[0] for f in L.STEP_RECORD_FIELDS], "formats"
 # struct qmhip_tick_record: one 2048-byte record per instance and controller tick (QMController below)
 TICK_RECORD = np.dtype({"names": [f[0] for f in L.TICK_RECORD_FIELDS], "formats": [f[1] if f[2] == 1 else (f[1], (f[2],)) for f in L.TICK_RECORD_FIELDS],
                         "offsets": [f[3] for f in L.TICK_RECORD_FIELDS], "itemsize": L.QM_TICK_BYTES})
+
+# struct qmhip_plan_record: one 512-byte record per node of a plan in task space (SqpMpc.plan_task_space, QMInterface.task_space); struct qmhip_foothold: one landing
+_rec_dtype = lambda fields, size: np.dtype({"names": [f[0] for f in fields], "formats": [f[1] if f[2] == 1 else (f[1], f[2] if isinstance(f[2], tuple) else (f[2],)) for f in fields],
+                                            "offsets": [f[3] for f in fields], "itemsize": size})
+PLAN_RECORD = _rec_dtype(L.PLAN_RECORD_FIELDS, L.QM_PLAN_BYTES)
+FOOTHOLD = _rec_dtype(L.FOOTHOLD_FIELDS, L.QM_FOOTHOLD_BYTES)
 
 
 class QmhipError(RuntimeError):
@@ -148,6 +155,17 @@ class QMInterface:
         x = np.zeros((B, 30))
         self._check(self.lib.qmhip_observe(self.h, B, _p(rbd), _p(x)), "qmhip_observe")
         return x
+
+    def task_space(self, x, u=None, mode=15, ee_ref=None):
+        """task-space records of caller-supplied states (qmhip_task_space_eval; QmVisualizer::publishDesiredTrajectory for target knots, publishObservation for an
+        observation): x [R][30] (or [30]), u [R][30] or None (zero inputs), mode [R] (or one for all rows), ee_ref [R][7] = pos + quat xyzw or None (ee_err = 0).
+        Returns [R] of dtype PLAN_RECORD (time = 0)"""
+        x = np.atleast_2d(_f(x)); R = x.shape[0]; assert x.shape == (R, 30)
+        u = None if u is None else _f(np.atleast_2d(u), (R, 30)); ee = None if ee_ref is None else _f(np.broadcast_to(np.asarray(ee_ref, float), (R, 7)))
+        md = np.ascontiguousarray(np.broadcast_to(np.asarray(mode, np.int32), (R,)), dtype=np.int32)
+        rec = np.zeros(R, PLAN_RECORD)
+        self._check(self.lib.qmhip_task_space_eval(self.h, R, _p(x), _p(u), _pi(md), _p(ee), rec.ctypes.data_as(C.c_void_p)), "qmhip_task_space_eval")
+        return rec
 
     def set_gain(self, name, value):
         """one field of the reference's dynamic_reconfigure config qm_wbc::WbcWeightConfig by NAME (WbcBase::dynamicCallback, WbcBase.cpp:69-116); False for a field
@@ -322,6 +340,21 @@ class SqpMpc:
         xd = np.zeros((B, 30)); u = np.zeros((B, 30)); mode = np.zeros(B, np.int32); cov = np.zeros(B, np.int32); seq = C.c_int64(0)
         self.itf._check(self.lib.qmhip_policy_eval_published(self.itf.h, B, _p(t), _p(xm), _p(xd), _p(u), _pi(mode), _pi(cov), C.byref(seq)), "qmhip_policy_eval_published")
         return xd, u, mode, cov, seq.value
+
+    def plan_task_space(self):
+        """the last solve's plan in task space (qmhip_plan_task_space; QmVisualizer::publishOptimizedStateTrajectory): (records [B][max_nodes] of dtype PLAN_RECORD,
+        num_nodes [B]); records at or behind num_nodes[b] are zero"""
+        B, nm = self.B, self.itf.max_nodes
+        rec = np.zeros((B, nm), PLAN_RECORD); nn = np.zeros(B, np.int32)
+        self.itf._check(self.lib.qmhip_plan_task_space(self.itf.h, B, rec.ctypes.data_as(C.c_void_p), _pi(nn)), "qmhip_plan_task_space")
+        return rec, nn
+
+    def plan_footholds(self, cap=16):
+        """where the feet land inside the planned horizon (qmhip_plan_footholds): (footholds [B][cap] of dtype FOOTHOLD ordered by (event, foot), count [B]); count[b]
+        is the full number of landings, of which the first min(count[b], cap) are written"""
+        B = self.B; fh = np.zeros((B, int(cap)), FOOTHOLD); cnt = np.zeros(B, np.int32)
+        self.itf._check(self.lib.qmhip_plan_footholds(self.itf.h, B, int(cap), fh.ctypes.data_as(C.c_void_p) if cap else None, _pi(cnt)), "qmhip_plan_footholds")
+        return fh, cnt
 
     def feedback(self):
         """the linear controller of the last solve as ocs2::LinearController holds it (qmhip_mpc_download_feedback): (gain [B][max_nodes][30][30], uff [B][max_nodes][30]) on the

@@ -20,6 +20,7 @@
 #include "qm_io_pipeline.h"
 #include "qm_tick_pipeline.h"
 #include "qm_publish_pipeline.h"
+#include "qm_plan_pipeline.h"
 
 static thread_local std::string g_create_error;      // per calling thread: qmhip_last_error(NULL) is the error of THIS thread's last failed create
 
@@ -48,7 +49,7 @@ struct HipBackend {
     const void* p = (const void*)k;
     if (p == (const void*)qm_grid_kernel || p == (const void*)qm_grid_nodes_kernel || p == (const void*)qm_save_grid_kernel || p == (const void*)qm_advance_kernel) return "grid"; if (p == (const void*)qm_lq_kernel || p == (const void*)qm_lq_dbg_kernel || p == (const void*)qm_lq_ipm_kernel) return "lq"; if (p == (const void*)qm_lq_m18_kernel) return "lq_m18"; if (p == (const void*)qm_lq_kin_kernel) return "lq_kin"; if (p == (const void*)qm_riccati_kernel || p == (const void*)qm_riccati_prof_kernel) return "riccati";
     if (p == (const void*)qm_ls_eval_kernel || p == (const void*)qm_ls_eval_dense_kernel || p == (const void*)qm_ls_eval_ipm_kernel) return "ls_eval";
-    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel) return "rollout"; if (p == (const void*)qm_sim_kernel) return "sim"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_policy_fb_kernel || p == (const void*)qm_policy_fb_pub_kernel) return "policy_fb"; if (p == (const void*)qm_policy_publish_kernel) return "publish"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io"; if (p == (const void*)qm_tick_state_kernel || p == (const void*)qm_tick_pack_kernel) return "tick";
+    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel) return "rollout"; if (p == (const void*)qm_sim_kernel) return "sim"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_policy_fb_kernel || p == (const void*)qm_policy_fb_pub_kernel) return "policy_fb"; if (p == (const void*)qm_policy_publish_kernel) return "publish"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io"; if (p == (const void*)qm_tick_state_kernel || p == (const void*)qm_tick_pack_kernel) return "tick"; if (p == (const void*)qm_plan_nodes_kernel) return "plan_nodes"; if (p == (const void*)qm_plan_states_kernel) return "plan_states"; if (p == (const void*)qm_plan_footholds_kernel) return "plan_footholds";
     return "ls_misc";
   }
   template <class K, class A> void launch(K kernel, int grid, int block, size_t lds, const A& args) {
@@ -129,7 +130,7 @@ struct HipBackend {
 struct qmhip_ctx {
   int device = 0, max_batch = 0, max_nodes = 0, max_ref = 0, max_ev = 0;
   double mb[MB_SIZE], st[ST_SIZE];
-  HipBackend bk; QmMpcPipeline<HipBackend> mpc; QmWbcPipeline<HipBackend> wbc; QmFrontPipeline<HipBackend> front; QmSimPipeline<HipBackend> sim; QmHoqpPipeline<HipBackend> hoqp; QmIoPipeline<HipBackend> io; QmTickPipeline<HipBackend> tick; QmPublishPipeline<HipBackend> pub;
+  HipBackend bk; QmMpcPipeline<HipBackend> mpc; QmWbcPipeline<HipBackend> wbc; QmFrontPipeline<HipBackend> front; QmSimPipeline<HipBackend> sim; QmHoqpPipeline<HipBackend> hoqp; QmIoPipeline<HipBackend> io; QmTickPipeline<HipBackend> tick; QmPublishPipeline<HipBackend> pub; QmPlanPipeline<HipBackend> plan;
   // qmhip_policy_eval_published: a stream, staging and device buffers of its own, serialised among evaluators by eval_mu — an evaluation never takes `mu` below
   std::mutex eval_mu; hipStream_t stream_p = nullptr; char* pe_pin = nullptr; char* pe_dev = nullptr;
   std::recursive_mutex mu;      // serialises the entry points of this context
@@ -138,7 +139,7 @@ struct qmhip_ctx {
   char* tick_pin = nullptr;     // pinned host staging of the control-tick path (qmhip_wbc_step): [inputs of max_batch instances | outputs]
   std::string error; int lastB = 0; bool have_solution = false; int front_B = 0; long sim_ticks = 0;
   hipEvent_t ev_meas = nullptr; bool meas_pending = false;      // streamed step I/O: "the synthetic measured state of the last submitted step has read x0" (the next submit's copy of x0 waits for it on the device)
-  qmhip_ctx() : mpc(bk), wbc(bk), front(bk), sim(bk), hoqp(bk), io(bk), tick(bk), pub(bk) {}
+  qmhip_ctx() : mpc(bk), wbc(bk), front(bk), sim(bk), hoqp(bk), io(bk), tick(bk), pub(bk), plan(bk) {}
   void fail(const std::string& m) { error = m; }
   // getModeSchedule on the device GaitSchedule -> the solver's schedule buffers; from here on its sticky status speaks for the schedule of this batch (until the host supplies one)
   void gait_schedule(int B, double horizon) { front.gait_schedule(mpc.d, B, horizon); mpc.front_status = front.f.gs_status; mpc.front_B = B; }
@@ -260,7 +261,7 @@ int qmhip_create_wbc_context(const qmhip_ctx* c, int max_batch, qmhip_ctx** out)
   return create_common(c->mb, c->st, c->device, max_batch, 3, 1, 1, out, true);      // same model / settings values, own device copies, own streams: nothing mutable is shared
 }
 void qmhip_destroy(qmhip_ctx* c) {
-  if (!c) return; hipSetDevice(c->device); c->bk.sync(); if (c->bk.stream_c) hipStreamSynchronize(c->bk.stream_c); c->io.release(); c->tick.release(); if (c->stream_p) hipStreamSynchronize(c->stream_p); c->pub.release(); if (c->pe_pin) hipHostFree(c->pe_pin); if (c->pe_dev) hipFree(c->pe_dev); if (c->stream_p) hipStreamDestroy(c->stream_p); if (c->ev_meas) hipEventDestroy(c->ev_meas); if (c->bk.ev_io_a) { hipEventDestroy(c->bk.ev_io_a); hipEventDestroy(c->bk.ev_io_b); } if (c->dl_dev) hipFree(c->dl_dev); if (c->dl_pin) hipHostFree(c->dl_pin); if (c->tick_pin) hipHostFree(c->tick_pin); c->mpc.release(); c->wbc.release(); c->front.release(); c->sim.release(); c->hoqp.release();
+  if (!c) return; hipSetDevice(c->device); c->bk.sync(); if (c->bk.stream_c) hipStreamSynchronize(c->bk.stream_c); c->io.release(); c->tick.release(); if (c->stream_p) hipStreamSynchronize(c->stream_p); c->pub.release(); c->plan.release(); if (c->pe_pin) hipHostFree(c->pe_pin); if (c->pe_dev) hipFree(c->pe_dev); if (c->stream_p) hipStreamDestroy(c->stream_p); if (c->ev_meas) hipEventDestroy(c->ev_meas); if (c->bk.ev_io_a) { hipEventDestroy(c->bk.ev_io_a); hipEventDestroy(c->bk.ev_io_b); } if (c->dl_dev) hipFree(c->dl_dev); if (c->dl_pin) hipHostFree(c->dl_pin); if (c->tick_pin) hipHostFree(c->tick_pin); c->mpc.release(); c->wbc.release(); c->front.release(); c->sim.release(); c->hoqp.release();
   for (auto e : c->bk.pool) hipEventDestroy(e); if (c->bk.ev_order) hipEventDestroy(c->bk.ev_order); hipEventDestroy(c->bk.ev_in); hipEventDestroy(c->bk.ev_wbc); hipStreamDestroy(c->bk.stream); hipStreamDestroy(c->bk.stream_b); if (c->bk.stream_c) hipStreamDestroy(c->bk.stream_c); delete c;
 }
 // the text is copied under the context lock into a per-thread buffer: the pointer stays valid (until this THREAD's next qmhip_last_error) even if another thread's
@@ -608,6 +609,31 @@ int qmhip_step_collect(qmhip_ctx* c, int B, qmhip_step_record* rec, double* ot, 
   return c->hipstate();
 }
 int qmhip_step_in_flight(const qmhip_ctx* c) { QM_GUARD(c); return c ? c->io.in_flight : 0; }
+
+
+// ---- planned task-space trajectories (k_plan.h, qm_plan_pipeline.h): the arithmetic of qm::QmVisualizer, qm_interface/src/visualization/qm_visualization.cpp ----
+static int plan_ready(qmhip_ctx* c, int B, const char* fn) {
+  if (!c->have_solution) { c->fail(std::string(fn) + ": no solution available (no solve on this context since its creation, the last upload, reset or solver switch)"); return QMHIP_ERR_STATE; }
+  if (B != c->mpc.solved_B) { c->fail(std::string(fn) + ": B differs from the batch size of the last solve (the solver buffers are strided by it)"); return QMHIP_ERR_STATE; }
+  return QMHIP_OK;
+}
+// publishOptimizedStateTrajectory, qm_visualization.cpp:90-189
+int qmhip_plan_task_space(qmhip_ctx* c, int B, qmhip_plan_record* rec, int32_t* nn) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c || B <= 0 || B > c->max_batch || !rec) { if (c) c->fail("qmhip_plan_task_space: bad argument"); return QMHIP_ERR_ARG; }
+  const int rc = plan_ready(c, B, "qmhip_plan_task_space"); if (rc != QMHIP_OK) return rc;
+  hipSetDevice(c->device); c->plan.task_space(c->mpc.d, B, rec, nn); return c->hipstate();
+}
+// its "Future footholds", qm_visualization.cpp:150-182
+int qmhip_plan_footholds(qmhip_ctx* c, int B, int cap, qmhip_foothold* out, int32_t* count) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c || B <= 0 || B > c->max_batch || cap < 0 || (cap > 0 && !out) || !count) { if (c) c->fail("qmhip_plan_footholds: bad argument"); return QMHIP_ERR_ARG; }
+  const int rc = plan_ready(c, B, "qmhip_plan_footholds"); if (rc != QMHIP_OK) return rc;
+  hipSetDevice(c->device); c->plan.footholds(c->mpc.d, B, cap, out, count); return c->hipstate();
+}
+// publishDesiredTrajectory, qm_visualization.cpp:194-251 (the target knots) and publishObservation, qm_visualization.cpp:267-283 (the observation)
+int qmhip_task_space_eval(qmhip_ctx* c, int R, const double* x, const double* u, const int32_t* mode, const double* ee_ref, qmhip_plan_record* rec) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c || R <= 0 || (long long)R > (long long)c->max_batch * c->max_nodes || !x || !mode || !rec) { if (c) c->fail("qmhip_task_space_eval: bad argument (1 <= R <= max_batch * max_nodes; x, mode and rec required)"); return QMHIP_ERR_ARG; }
+  hipSetDevice(c->device); c->plan.eval(c->mpc.d.mb, R, x, u, mode, ee_ref, rec); return c->hipstate();
+}
 
 // ---- streamed controller tick for a plant on the host (include/qmhip.h): measured rbd state in, hybrid joint command out ----
 // tick_submit enqueues one QMController::update for the batch on the MPC stream — the stream qmhip_closed_loop_sim runs its ticks on, with the same launches

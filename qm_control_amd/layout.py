@@ -7,7 +7,7 @@ _HDR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 DEFINES = {}
 with open(_HDR) as _fh:
     for _line in _fh:
-        _m = re.match(r"#define\s+((?:MB|ST|QM|PR)_\w+)\s+(\d+)\s", _line)
+        _m = re.match(r"#define\s+((?:MB|ST|QM|PR|PT)_\w+)\s+(\d+)\s", _line)
         if _m:
             DEFINES[_m.group(1)] = int(_m.group(2))
             continue
@@ -30,3 +30,9 @@ TICK_RECORD_FIELDS = [("cmd", "<f8", 90, 8 * QM_TICK_CMD), ("x_obs", "<f8", 30, 
                       ("n_nodes", "<i4", 1, _TI + 4 * QM_TICK_I_NODES), ("qp_status", "<i4", 3, _TI + 4 * QM_TICK_I_QP), ("safety", "<i4", 1, _TI + 4 * QM_TICK_I_SAFETY),
                       ("stopped", "<i4", 1, _TI + 4 * QM_TICK_I_STOPPED), ("mpc_ran", "<i4", 1, _TI + 4 * QM_TICK_I_MPCRAN), ("tick", "<i4", 1, _TI + 4 * QM_TICK_I_TICK),
                       ("reserved", "<i4", 13, _TI + 4 * (QM_TICK_I_TICK + 1))]
+
+# struct qmhip_plan_record (include/qmhip_layout.h), same form, from the PT_* word offsets; struct qmhip_foothold
+PLAN_RECORD_FIELDS = [("time", "<f8", 1, 8 * PT_TIME), ("mode", "<i4", 1, 8 * PT_MODE), ("contact_mask", "<i4", 1, 8 * PT_MODE + 4), ("base_pos", "<f8", 3, 8 * PT_BASE_POS), ("base_zyx", "<f8", 3, 8 * PT_BASE_ZYX),
+                      ("foot_pos", "<f8", (4, 3), 8 * PT_FOOT_POS), ("foot_vel", "<f8", (4, 3), 8 * PT_FOOT_VEL), ("foot_force", "<f8", (4, 3), 8 * PT_FOOT_FORCE),
+                      ("ee_pos", "<f8", 3, 8 * PT_EE_POS), ("ee_quat", "<f8", 4, 8 * PT_EE_QUAT), ("ee_err", "<f8", 6, 8 * PT_EE_ERR), ("cop", "<f8", 3, 8 * PT_COP), ("spare", "<f8", 4, 8 * PT_SPARE)]
+FOOTHOLD_FIELDS = [("time", "<f8", 1, 0), ("leg", "<i4", 1, 8), ("event", "<i4", 1, 12), ("pos", "<f8", 3, 16)]
