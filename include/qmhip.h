@@ -372,8 +372,40 @@ int qmhip_closed_loop_sim(qmhip_ctx* ctx, int B, int n_ticks, double period, int
  *        instance and is counted (qmhip_policy_published_info).  With ST_FEEDBACK_POLICY = 0 a window changes nothing in this loop. */
 int qmhip_closed_loop_sim_pipelined(qmhip_ctx* ctx, int B, int n_ticks, double period, int n_substeps, int mpc_every, double horizon, double arm_kp, double arm_kd);
 
+/* ---- episode monitor: what happened DURING a run of the two device loops above — per-instance running statistics folded on the device behind every tick, and an optional
+ *      decimated trace of raw samples; both are read back with one copy each.  Records: struct qmhip_episode_summary, 256 bytes, and struct qmhip_episode_sample, 512 bytes:
+ *      qmhip_layout.h.  Off by default: both loops then launch what they launch without it.  On, the monitor's kernels (csrc/kernels/k_episode.h) only READ the loop's
+ *      buffers, so every output of the loop keeps its bits.
+ *      episode_monitor: switches it on with fall thresholds (min_base_z on rbd[5], max_tilt on |roll| = |rbd[2]| and |pitch| = |rbd[1]|; strict comparisons) and a trace of
+ *        up to trace_cap samples, one every trace_every ticks (both 0: no trace); NULL switches it off and frees its buffers.  Calling it again starts over.
+ *      An episode starts with qmhip_sim_reset (monitor on): records cleared, the anchor is the end-effector pose rbd[48:55] of the reset state unless episode_set_anchor is
+ *        called afterwards, the contact flags "before the first tick" are the reset state's.  Every tick of qmhip_closed_loop_sim / _pipelined of the reset's B is then folded:
+ *        FALL RULE — the fall check comes first; from the tick that trips it on only `ticks` and `t_last` advance, the tripping tick itself is not folded into maxima, sums
+ *        and counters (a non-finite state never reaches an accumulator; fall_cause 8).  t_first is the time behind the first folded tick, fallen or not.  An MPC call counts
+ *        iff the instance had not fallen BEFORE the tick the call observed at, in both loops.  contact_mismatch compares the measured flag behind the tick with the stance bit
+ *        of the mode the tick's policy returned.  max_ee_ang_dev is the rotation angle 4 asin(d / 2), d = min(|q - q_a|, |q + q_a|).
+ *      Samples are raw copies, taken on every tick whose index since the episode's start is a multiple of trace_every, fallen or not, into slot tick / trace_every while that
+ *        is below trace_cap; `mpc_status` is the status word of the last MPC call folded before the tick's fold (the pipelined loop folds a call behind its publication: the
+ *        ticks of an MPC period carry the status of the call published in front of them).  episode_trace hands out min(count, cap, trace_cap) samples, sample-major
+ *        [n][B] as on the device, and leaves the rest of `out` alone; *count keeps counting behind trace_cap, like qmhip_plan_footholds.
+ *      episode_fold: one tick of a plant the CALLER owns (the companion of qmhip_tick_submit) through the same kernels: the state behind the tick, what the tick's policy /
+ *        WBC returned, optionally the plant's status and — on a tick with an MPC call — the call's status word (it observed at this tick).  The first fold after
+ *        episode_monitor starts the episode: the anchor must have been set, and the first tick's own contact flags stand for the flags before it.
+ *      Reads run on the stream the synchronous loop's ticks run on and wait for that stream only (the pipelined loop has joined its streams when it returns).
+ *      QMHIP_ERR_STATE: monitor off, a WBC-only context, summary / trace of a B other than the episode's (or before any episode), the first fold without an anchor.
+ *      QMHIP_ERR_ARG: a NULL argument (fold: only sim_status / mpc_status may be NULL), B out of range or other than the running episode's, tick < 0, cap < 0, thresholds
+ *        that are not finite, trace_every < 0, trace_cap < 0, or one of the pair zero and the other not.  Profiling name: "episode". */
+typedef struct qmhip_episode_params { double min_base_z, max_tilt; int32_t trace_every, trace_cap; } qmhip_episode_params;
+int qmhip_episode_monitor(qmhip_ctx* ctx, const qmhip_episode_params* p /* NULL: off */);
+int qmhip_episode_set_anchor(qmhip_ctx* ctx, int B, const double* ee_pose /*[B][7] position + quaternion xyzw*/);
+int qmhip_episode_summary(qmhip_ctx* ctx, int B, struct qmhip_episode_summary* out /*[B]*/);
+int qmhip_episode_trace(qmhip_ctx* ctx, int B, int cap, qmhip_episode_sample* out /*[min(count, cap, trace_cap)][B]*/, int32_t* count);
+int qmhip_episode_fold(qmhip_ctx* ctx, int B, int tick, double period, const double* time /*[B]*/, const double* rbd /*[B][55]*/, const int32_t* contact /*[B][4]*/,
+                       const double* force /*[B][12]*/, const int32_t* mode /*[B]*/, const double* wbc_out /*[B][54]*/, const int32_t* qp_status /*[B][3]*/,
+                       const int32_t* sim_status /*[B] or NULL*/, const int32_t* mpc_status /*[B] or NULL: no MPC call on this tick*/);
+
 /* ---- instrumentation (ocs2 benchmark::RepeatedTimer analogue, QMController.cpp:145-147,321-323) ----
- * per-kernel HIP-event timing on the stream each kernel runs on; names: "grid","lq_kin","lq","riccati","ls_eval","ls_misc","policy","wbc","sim","plan_nodes","plan_states","plan_footholds".
+ * per-kernel HIP-event timing on the stream each kernel runs on; names: "grid","lq_kin","lq","riccati","ls_eval","ls_misc","policy","wbc","sim","plan_nodes","plan_states","plan_footholds","episode".
  * enable: 0 off, 1 a span around every launch, 2 only around the three modelled kernels "lq","riccati","wbc", 3 only around "lq" — the dominant kernel, all the
  * bench's timed region carries (two event records cost about one launch) */
 int qmhip_set_profiling(qmhip_ctx* ctx, int enable);

@@ -238,8 +238,76 @@ typedef struct qmhip_plan_record {
 /* one landing of one foot inside the planned horizon (qmhip_plan_footholds): event = index into the instance's schedule, leg in contact order */
 #define QM_FOOTHOLD_BYTES 40
 typedef struct qmhip_foothold { double time; int32_t leg, event; double pos[3]; } qmhip_foothold;
+
+/* episode monitor (qmhip.h, "episode monitor"): per-instance running statistics of a device loop, folded behind every tick by the kernels of csrc/kernels/k_episode.h.
+   EP_* are offsets in 8-byte WORDS of struct qmhip_episode_summary (32 words: 16 doubles, then 32 int32, two per word; EP_I_* are indices of those int32),
+   ES_* offsets in 8-byte words of struct qmhip_episode_sample (64 words: 60 doubles, then 8 int32).  Feet in CONTACT order LF RF LH RH; a mask is 8 LF + 4 RF + 2 LH + RH */
+#define EP_T_FIRST        0    /* plant time behind the first folded tick                                  */
+#define EP_T_LAST         1    /* plant time behind the last folded tick                                   */
+#define EP_T_FALL         2    /* plant time behind the tick that tripped the fall check; 0 while not fallen */
+#define EP_MIN_BASE_Z     3    /* min of rbd[5]; + infinity before the first tick                          */
+#define EP_MAX_ROLL       4    /* max |rbd[2]|                                                             */
+#define EP_MAX_PITCH      5    /* max |rbd[1]|                                                             */
+#define EP_MAX_SPEED      6    /* max |rbd[27:30]|                                                         */
+#define EP_MAX_EE_POS     7    /* max |rbd[48:51] - anchor position|                                       */
+#define EP_SUMSQ_EE_POS   8    /* sum of its squares (RMS = sqrt(sum / folded ticks))                      */
+#define EP_MAX_EE_ANG     9    /* max rotation angle between rbd[51:55] and the anchor quaternion          */
+#define EP_MAX_TAU_RATIO  10   /* max over joints of |tau_j| / effort limit                                */
+#define EP_MAX_FRICTION   11   /* max over feet with f_z > 0 of |f_xy| / f_z                               */
+#define EP_MAX_NORMAL     12   /* max f_z                                                                  */
+#define EP_JOINT_WORK     13   /* sum over ticks of period * sum_j |tau_j qdot_j|                          */
+#define EP_SPARE          14   /* [2] zero                                                                 */
+#define EP_INTS           16   /* first word of the int32 part                                             */
+#define EP_I_TICKS        0    /* folded ticks (the only counter that advances behind a fall)              */
+#define EP_I_FALL_TICK    1    /* tick that tripped the fall check; -1: none                               */
+#define EP_I_FALL_CAUSE   2    /* QM_FALL_* bits of that tick                                              */
+#define EP_I_SIM_BAD      3    /* ticks with a non-zero plant status                                       */
+#define EP_I_MPC_CALLS    4    /* MPC calls folded (words 18 .. 20 belong to qm_episode_mpc_kernel)        */
+#define EP_I_MPC_FAILS    5    /* ... with a status < 0                                                    */
+#define EP_I_MPC_WARN_OR  6    /* OR of the positive status words                                          */
+#define EP_I_MPC_LAST_FAIL 7   /* the last negative status word                                            */
+#define EP_I_MPC_FIRST_FAIL 8  /* tick the first failing call observed at; -1: none                        */
+#define EP_I_RESERVED     9    /* 0                                                                        */
+#define EP_I_WBC_BAD      10   /* [3] ticks with a non-zero qp_status, per priority level                  */
+#define EP_I_AIRBORNE     13   /* ticks with no foot in contact                                            */
+#define EP_I_MISMATCH     14   /* [4] ticks whose measured contact flag differs from the planned stance bit */
+#define EP_I_TOUCHDOWN    18   /* [4] 0 -> 1 transitions of the contact flag                               */
+#define EP_I_TAU_OVER     22   /* ticks with a torque ratio > 1                                            */
+#define EP_I_SPARE        23   /* [9] zero                                                                 */
+#define QM_EP_WORDS 32
+#define QM_EP_BYTES 256
+#define QM_FALL_HEIGHT 1       /* rbd[5] < min_base_z                                                      */
+#define QM_FALL_ROLL   2       /* |rbd[2]| > max_tilt                                                      */
+#define QM_FALL_PITCH  4       /* |rbd[1]| > max_tilt                                                      */
+#define QM_FALL_NONFINITE 8    /* an entry of rbd is not finite                                            */
+/* (a struct TAG, no typedef: qmhip_episode_summary is also the entry point that fills it — write `struct qmhip_episode_summary`) */
+struct qmhip_episode_summary {
+  double t_first, t_last, t_fall, min_base_z, max_abs_roll, max_abs_pitch, max_base_speed, max_ee_pos_dev, sum_sq_ee_pos_dev, max_ee_ang_dev, max_tau_ratio, max_friction_ratio,
+         max_normal_force, joint_work, spare[2];
+  int32_t ticks, fall_tick, fall_cause, sim_bad_ticks, mpc_calls, mpc_fail_calls, mpc_warn_or, mpc_last_fail, mpc_first_fail_tick, reserved, wbc_bad_ticks[3], airborne_ticks,
+          contact_mismatch_ticks[4], touchdowns[4], tau_over_ticks, ispare[9];
+};
+#define ES_TIME     0    /* plant time behind the tick                                                     */
+#define ES_RBD      1    /* [55] measured state behind the tick                                            */
+#define ES_FORCE_Z  56   /* [4] normal contact forces                                                      */
+#define ES_INTS     60   /* int32: tick, planned mode | measured contact mask, last folded MPC status | qp_status[0], [1] | qp_status[2], plant status */
+#define QM_ES_WORDS 64
+#define QM_ES_BYTES 512
+typedef struct qmhip_episode_sample {
+  double time, rbd[55], force_z[4];
+  int32_t tick, mode, contact_mask, mpc_status, qp_status[3], sim_status;
+} qmhip_episode_sample;
 #ifdef __cplusplus
 #include <stddef.h>
+static_assert(sizeof(struct qmhip_episode_summary) == QM_EP_BYTES && QM_EP_WORDS * 8 == QM_EP_BYTES && 8 * EP_INTS + 4 * (EP_I_SPARE + 9) == QM_EP_BYTES, "qmhip_episode_summary is 32 eight-byte words");
+static_assert(offsetof(struct qmhip_episode_summary, t_fall) == 8 * EP_T_FALL && offsetof(struct qmhip_episode_summary, min_base_z) == 8 * EP_MIN_BASE_Z && offsetof(struct qmhip_episode_summary, max_ee_pos_dev) == 8 * EP_MAX_EE_POS &&
+              offsetof(struct qmhip_episode_summary, joint_work) == 8 * EP_JOINT_WORK && offsetof(struct qmhip_episode_summary, spare) == 8 * EP_SPARE && offsetof(struct qmhip_episode_summary, ticks) == 8 * EP_INTS &&
+              offsetof(struct qmhip_episode_summary, mpc_calls) == 8 * EP_INTS + 4 * EP_I_MPC_CALLS && offsetof(struct qmhip_episode_summary, mpc_first_fail_tick) == 8 * EP_INTS + 4 * EP_I_MPC_FIRST_FAIL &&
+              offsetof(struct qmhip_episode_summary, wbc_bad_ticks) == 8 * EP_INTS + 4 * EP_I_WBC_BAD && offsetof(struct qmhip_episode_summary, contact_mismatch_ticks) == 8 * EP_INTS + 4 * EP_I_MISMATCH &&
+              offsetof(struct qmhip_episode_summary, touchdowns) == 8 * EP_INTS + 4 * EP_I_TOUCHDOWN && offsetof(struct qmhip_episode_summary, tau_over_ticks) == 8 * EP_INTS + 4 * EP_I_TAU_OVER &&
+              offsetof(struct qmhip_episode_summary, ispare) == 8 * EP_INTS + 4 * EP_I_SPARE, "EP_* are the word / int32 offsets of qmhip_episode_summary");
+static_assert(sizeof(qmhip_episode_sample) == QM_ES_BYTES && QM_ES_WORDS * 8 == QM_ES_BYTES && offsetof(qmhip_episode_sample, rbd) == 8 * ES_RBD && offsetof(qmhip_episode_sample, force_z) == 8 * ES_FORCE_Z &&
+              offsetof(qmhip_episode_sample, tick) == 8 * ES_INTS && offsetof(qmhip_episode_sample, sim_status) == 8 * ES_INTS + 28, "ES_* are the word offsets of qmhip_episode_sample");
 static_assert(sizeof(qmhip_plan_record) == QM_PLAN_BYTES && QM_PLAN_WORDS * 8 == QM_PLAN_BYTES, "qmhip_plan_record is 64 eight-byte words");
 static_assert(offsetof(qmhip_plan_record, mode) == 8 * PT_MODE && offsetof(qmhip_plan_record, contact_mask) == 8 * PT_MODE + 4 && offsetof(qmhip_plan_record, base_pos) == 8 * PT_BASE_POS &&
               offsetof(qmhip_plan_record, base_zyx) == 8 * PT_BASE_ZYX && offsetof(qmhip_plan_record, foot_pos) == 8 * PT_FOOT_POS && offsetof(qmhip_plan_record, foot_vel) == 8 * PT_FOOT_VEL &&

@@ -28,6 +28,7 @@ EXPORTS = ["qmhip_create", "qmhip_create_from_blobs", "qmhip_create_wbc_context"
            "qmhip_target_reset", "qmhip_target_from_command", "qmhip_target_download",
            "qmhip_step_submit", "qmhip_step_collect", "qmhip_step_in_flight",
            "qmhip_plan_task_space", "qmhip_plan_footholds", "qmhip_task_space_eval",
+           "qmhip_episode_monitor", "qmhip_episode_set_anchor", "qmhip_episode_summary", "qmhip_episode_trace", "qmhip_episode_fold",
            "qmhip_tick_reset", "qmhip_tick_submit", "qmhip_tick_collect", "qmhip_observe", "qmhip_sim_get_rbd",
            "qmhip_sim_set_params", "qmhip_sim_set_controller", "qmhip_sim_reset", "qmhip_sim_set_command", "qmhip_sim_step", "qmhip_sim_get_state", "qmhip_closed_loop_sim", "qmhip_closed_loop_sim_pipelined"]
 
@@ -44,6 +45,24 @@ _rec_dtype = lambda fields, size: np.dtype({"names": [f[0] for f in fields], "fo
                                             "offsets": [f[3] for f in fields], "itemsize": size})
 PLAN_RECORD = _rec_dtype(L.PLAN_RECORD_FIELDS, L.QM_PLAN_BYTES)
 FOOTHOLD = _rec_dtype(L.FOOTHOLD_FIELDS, L.QM_FOOTHOLD_BYTES)
+# struct qmhip_episode_summary: one 256-byte record per instance of a monitored episode; struct qmhip_episode_sample: one 512-byte raw sample (QMHWSim.monitor)
+EPISODE_SUMMARY = _rec_dtype(L.EPISODE_SUMMARY_FIELDS, L.QM_EP_BYTES)
+EPISODE_SAMPLE = _rec_dtype(L.EPISODE_SAMPLE_FIELDS, L.QM_ES_BYTES)
+FALL_HEIGHT, FALL_ROLL, FALL_PITCH, FALL_NONFINITE = L.QM_FALL_HEIGHT, L.QM_FALL_ROLL, L.QM_FALL_PITCH, L.QM_FALL_NONFINITE
+
+
+class _EpisodeParams(C.Structure):
+    _fields_ = [("min_base_z", C.c_double), ("max_tilt", C.c_double), ("trace_every", C.c_int32), ("trace_cap", C.c_int32)]
+
+
+def episode_fold(interface, tick, period, time, rbd, contact, force, mode, wbc_out, qp_status, sim_status=None, mpc_status=None):
+    """qmhip_episode_fold: one tick of a plant the caller owns into the episode monitor (the companion of QMController.update): the state BEHIND the tick (time [B], rbd
+    [B][55], contact [B][4], force [B][12]), what the tick's policy / WBC returned (mode [B], wbc_out [B][54], qp_status [B][3]), optionally the plant's status [B] and, on
+    a tick with an MPC call, the call's status word [B].  The first fold after QMHWSim.monitor() starts the episode (set_anchor first)."""
+    rbd = _f(rbd); B = rbd.shape[0]; i32 = lambda a, shape: None if a is None else np.ascontiguousarray(np.broadcast_to(a, shape), dtype=np.int32)
+    t = _f(np.broadcast_to(time, (B,))); ct = i32(contact, (B, 4)); fo = _f(force, (B, 12)); mo = i32(mode, (B,)); wo = _f(wbc_out, (B, 54)); qp = i32(qp_status, (B, 3)); ss = i32(sim_status, (B,)); ms = i32(mpc_status, (B,))
+    assert rbd.shape == (B, 55)
+    interface._check(interface.lib.qmhip_episode_fold(interface.h, B, int(tick), C.c_double(period), _p(t), _p(rbd), _pi(ct), _p(fo), _pi(mo), _p(wo), _pi(qp), _pi(ss), _pi(ms)), "qmhip_episode_fold")
 
 
 class QmhipError(RuntimeError):
@@ -471,6 +490,36 @@ class QMHWSim:
         fn = self.lib.qmhip_closed_loop_sim_pipelined if pipelined else self.lib.qmhip_closed_loop_sim     # pipelined: the MPC beside the ticks, one period of latency
         self.itf._check(fn(self.itf.h, self.B, int(n_ticks), C.c_double(period), int(n_substeps), int(mpc_every), C.c_double(horizon), C.c_double(arm_kp), C.c_double(arm_kd)), "qmhip_closed_loop_sim")
 
+    def monitor(self, min_base_z=0.2, max_tilt=0.8, trace_every=0, trace_cap=0):
+        """episode monitor (qmhip_episode_monitor): per-instance statistics of every tick of closed_loop() folded on the device, a fall when the base height drops below
+        min_base_z or |roll| / |pitch| exceed max_tilt, optionally a trace of up to trace_cap raw samples, one every trace_every ticks.  monitor(None) switches it off.
+        The next reset() starts the episode; read it with episode_summary() / episode_trace()"""
+        if min_base_z is None:
+            self.itf._check(self.lib.qmhip_episode_monitor(self.itf.h, None), "qmhip_episode_monitor"); self._trace_cap = 0; return
+        p = _EpisodeParams(float(min_base_z), float(max_tilt), int(trace_every), int(trace_cap))
+        self.itf._check(self.lib.qmhip_episode_monitor(self.itf.h, C.byref(p)), "qmhip_episode_monitor")
+        self._trace_cap = int(trace_cap)
+
+    def set_anchor(self, ee_pose):
+        """end-effector anchor [B][7] (position + quaternion xyzw) of the deviation statistics; without it the anchor is the reset state's end-effector pose"""
+        ee = _f(ee_pose); assert ee.ndim == 2 and ee.shape[1] == 7
+        self.itf._check(self.lib.qmhip_episode_set_anchor(self.itf.h, ee.shape[0], _p(ee)), "qmhip_episode_set_anchor")
+
+    def episode_summary(self, B=None):
+        """records [B] of dtype EPISODE_SUMMARY of the running episode"""
+        B = self.B if B is None else int(B); out = np.zeros(B, EPISODE_SUMMARY)
+        self.itf._check(self.lib.qmhip_episode_summary(self.itf.h, B, out.ctypes.data_as(C.c_void_p)), "qmhip_episode_summary")
+        return out
+
+    def episode_trace(self, cap=None, B=None):
+        """(samples [n][B] of dtype EPISODE_SAMPLE, count): n = min(count, cap) samples the trace holds, count the number of sampled ticks (it keeps counting behind trace_cap)"""
+        B = self.B if B is None else int(B); n = np.zeros(1, np.int32)
+        if cap is None:
+            self.itf._check(self.lib.qmhip_episode_trace(self.itf.h, B, 0, None, _pi(n)), "qmhip_episode_trace"); cap = int(n[0])
+        out = np.zeros((int(cap), B), EPISODE_SAMPLE)
+        self.itf._check(self.lib.qmhip_episode_trace(self.itf.h, B, int(cap), out.ctypes.data_as(C.c_void_p) if cap else None, _pi(n)), "qmhip_episode_trace")
+        return out[:min(int(n[0]), int(cap), getattr(self, "_trace_cap", 0))], int(n[0])
+
     def rbd(self):
         """(rbd [B][55], contact [B][4]) of the plant's current state, without stepping (qmhip_sim_get_rbd)"""
         B = self.B; rbd = np.zeros((B, 55)); contact = np.zeros((B, 4), np.int32)
@@ -512,6 +561,10 @@ class QMController:
     def update(self, time, rbd, contact=None, *, horizon, period):
         self.update_submit(time, rbd, contact, horizon=horizon, period=period)
         return self.update_collect()
+
+    def fold(self, tick, period, time, rbd, contact, force, mode, wbc_out, qp_status, sim_status=None, mpc_status=None):
+        """episode_fold() on this controller's interface: the tick just collected and the plant state behind it into the episode monitor"""
+        episode_fold(self.itf, tick, period, time, rbd, contact, force, mode, wbc_out, qp_status, sim_status, mpc_status)
 
 
 GAIT_MAX_PHASES, GAIT_EVENT_SLOTS = 16, 256

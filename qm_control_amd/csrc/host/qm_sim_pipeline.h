@@ -72,15 +72,19 @@ struct QmSimPipeline {
 // feedback (ST_FEEDBACK_POLICY; multiple-shooting solvers only — the caller checks): the tick evaluates the SQP's linear controller at its estimated centroidal state
 // (evaluatePolicy(time, currentObservation_.state, ...), QMController.cpp:139-142, with sqp.useFeedbackPolicy) in place of the feed-forward policy: the observation the MPC
 // call of this tick was given, or the same estimate built for this tick alone
-template <class BK, class PreMpc>
+// epi (a QmEpisodePipeline<BK> that is switched on, qm_episode_pipeline.h): the episode monitor folds every MPC call behind its solve and every tick behind its simulation
+// step, reading the buffers the tick left.  Without it (QmNoEpisode, a null pointer, a monitor that is off) the loop launches what it launches without the feature
+struct QmNoEpisode { static constexpr bool enabled = false; };
+template <class BK, class PreMpc, class Epi = QmNoEpisode>
 void qm_closed_loop_sim_ticks(BK& bk, QmMpcPipeline<BK>& mpc, QmWbcPipeline<BK>& wbc, QmSimPipeline<BK>& sim, long& sim_ticks, int B, int n_ticks, double period, int n_substeps,
-                              int mpc_every, double horizon, double arm_kp, double arm_kd, int sqp_iters, PreMpc pre_mpc, bool feedback = false) {
+                              int mpc_every, double horizon, double arm_kp, double arm_kd, int sqp_iters, PreMpc pre_mpc, bool feedback = false, Epi* epi = nullptr) {
   for (int k = 0; k < n_ticks; ++k) {
     const bool mpc_tick = (sim_ticks % mpc_every) == 0;
     if (mpc_tick) {
       sim.observe(mpc.d, B);
       pre_mpc();
       mpc.grid(B, horizon, true); for (int it = 0; it < sqp_iters; ++it) mpc.sqp_iteration(B, 14, it + 1 == sqp_iters);
+      if constexpr (Epi::enabled) { if (epi && epi->on) epi->mpc_fold(mpc.d, B, sim_ticks); }
     }
     if (feedback) { if (!mpc_tick) sim.estimate(mpc.d, B); wbc.policy_fb(mpc.d, B, sim.s.time, mpc_tick ? mpc.d.x0 : sim.s.x_est); }
     else bk.launch(qm_policy_kernel, (B + 63) / 64, 64, 0, wbc.pargs(mpc.d, B, sim.s.time));
@@ -90,6 +94,7 @@ void qm_closed_loop_sim_ticks(BK& bk, QmMpcPipeline<BK>& mpc, QmWbcPipeline<BK>&
     wbc.step(mpc.d, B, period, sim.controller == 1 ? 1 : 0, sim.s.rbd, sim.s.time);      // QMMpcController::setupWbc installs HierarchicalMpcWbc (QMController.cpp:410-414)
     sim.command(B, wbc.w.x_des, wbc.w.u_des, wbc.w.out, arm_kp, arm_kd);
     sim.step(mpc.d.mb, B, period, n_substeps);
+    if constexpr (Epi::enabled) { if (epi && epi->on) epi->tick_fold(mpc.d.mb, B, sim_ticks, period, sim.s, wbc.w); }
     ++sim_ticks;
   }
 }
@@ -103,10 +108,12 @@ void qm_closed_loop_sim_ticks(BK& bk, QmMpcPipeline<BK>& mpc, QmWbcPipeline<BK>&
 // pub (a QmPublishPipeline<BK> with a window, qm_publish_pipeline.h; ST_FEEDBACK_POLICY = 1 — the caller checks both): the publication also snapshots the first nodes' gain
 // records, and every tick evaluates the published LINEAR controller at its estimated centroidal state, as the synchronous loop does on the live records.  Without it
 // (QmNoPublish) the loop is the feed-forward one, launch for launch
+// epi: the episode monitor as above; an MPC call is folded on the TICK stream behind its publication — behind stream_order(0, 1), never while a solve runs on the other
+// stream — with the tick it observed at
 struct QmNoPublish { static constexpr bool enabled = false; };
-template <class BK, class PreMpc, class Pub = QmNoPublish>
+template <class BK, class PreMpc, class Pub = QmNoPublish, class Epi = QmNoEpisode>
 void qm_closed_loop_sim_pipelined(BK& bk, QmMpcPipeline<BK>& mpc, QmWbcPipeline<BK>& wbc, QmSimPipeline<BK>& sim, long& sim_ticks, int B, int n_ticks, double period, int n_substeps,
-                                  int mpc_every, double horizon, double arm_kp, double arm_kd, int sqp_iters, PreMpc pre_mpc, Pub* pub = nullptr) {
+                                  int mpc_every, double horizon, double arm_kp, double arm_kd, int sqp_iters, PreMpc pre_mpc, Pub* pub = nullptr, Epi* epi = nullptr) {
   auto solve = [&]() { pre_mpc(); mpc.grid(B, horizon, true); for (int it = 0; it < sqp_iters; ++it) mpc.sqp_iteration(B, 14, it + 1 == sqp_iters); };
   auto publish = [&]() {
     if constexpr (Pub::enabled) { if (pub) { pub->publish(mpc.d, B, true); sim.s.p_valid = true; return; } }
@@ -124,20 +131,23 @@ void qm_closed_loop_sim_pipelined(BK& bk, QmMpcPipeline<BK>& mpc, QmWbcPipeline<
       wbc.step(mpc.d, B, period, sim.controller == 1 ? 1 : 0, sim.s.rbd, sim.s.time);
       sim.command(B, wbc.w.x_des, wbc.w.u_des, wbc.w.out, arm_kp, arm_kd);
       sim.step(mpc.d.mb, B, period, n_substeps);
+      if constexpr (Epi::enabled) { if (epi && epi->on) epi->tick_fold(mpc.d.mb, B, sim_ticks, period, sim.s, wbc.w); }
       ++sim_ticks;
     }
   };
+  auto fold_mpc = [&](long t_obs) { if constexpr (Epi::enabled) { if (epi && epi->on) epi->mpc_fold(mpc.d, B, t_obs); } };
   for (int p = 0; p < n_ticks / mpc_every; ++p) {
+    const long t_obs = sim_ticks;
     bk.stream_select(1); sim.observe(mpc.d, B); bk.stream_order(1, 0);
     bool have = sim.s.p_valid && sim.s.p_xs != nullptr;
     if constexpr (Pub::enabled) { if (pub) { int k = -1; pub->book.info(nullptr, nullptr, &k, nullptr); have = sim.s.p_valid && k >= 0; } }      // (the two kinds of loop publish into buffers of their own)
     if (!have) {                                // no policy yet: solve first, then run the ticks of this period on it
       bk.stream_select(0); solve(); bk.stream_order(0, 1);
-      bk.stream_select(1); publish(); ticks();
+      bk.stream_select(1); publish(); fold_mpc(t_obs); ticks();
     } else {
       bk.stream_select(1); ticks();             // enqueued first: they run while the host waits inside the solve's line search
       bk.stream_select(0); solve(); bk.stream_order(0, 1);
-      bk.stream_select(1); publish();
+      bk.stream_select(1); publish(); fold_mpc(t_obs);
     }
     bk.stream_order(1, 0);                      // the next solve must not overwrite the solution before it has been published
   }

@@ -21,6 +21,8 @@
 #include "qm_tick_pipeline.h"
 #include "qm_publish_pipeline.h"
 #include "qm_plan_pipeline.h"
+#include "qm_episode_pipeline.h"
+static_assert(QM_EP_OK == QMHIP_OK && QM_EP_ERR_ARG == QMHIP_ERR_ARG && QM_EP_ERR_STATE == QMHIP_ERR_STATE && sizeof(QmEpisodeParams) == sizeof(qmhip_episode_params), "qm_episode_pipeline.h restates the error codes and the parameter struct of qmhip.h");
 
 static thread_local std::string g_create_error;      // per calling thread: qmhip_last_error(NULL) is the error of THIS thread's last failed create
 
@@ -49,7 +51,7 @@ struct HipBackend {
     const void* p = (const void*)k;
     if (p == (const void*)qm_grid_kernel || p == (const void*)qm_grid_nodes_kernel || p == (const void*)qm_save_grid_kernel || p == (const void*)qm_advance_kernel) return "grid"; if (p == (const void*)qm_lq_kernel || p == (const void*)qm_lq_dbg_kernel || p == (const void*)qm_lq_ipm_kernel) return "lq"; if (p == (const void*)qm_lq_m18_kernel) return "lq_m18"; if (p == (const void*)qm_lq_kin_kernel) return "lq_kin"; if (p == (const void*)qm_riccati_kernel || p == (const void*)qm_riccati_prof_kernel) return "riccati";
     if (p == (const void*)qm_ls_eval_kernel || p == (const void*)qm_ls_eval_dense_kernel || p == (const void*)qm_ls_eval_ipm_kernel) return "ls_eval";
-    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel) return "rollout"; if (p == (const void*)qm_sim_kernel) return "sim"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_policy_fb_kernel || p == (const void*)qm_policy_fb_pub_kernel) return "policy_fb"; if (p == (const void*)qm_policy_publish_kernel) return "publish"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io"; if (p == (const void*)qm_tick_state_kernel || p == (const void*)qm_tick_pack_kernel) return "tick"; if (p == (const void*)qm_plan_nodes_kernel) return "plan_nodes"; if (p == (const void*)qm_plan_states_kernel) return "plan_states"; if (p == (const void*)qm_plan_footholds_kernel) return "plan_footholds";
+    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel) return "rollout"; if (p == (const void*)qm_sim_kernel) return "sim"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_policy_fb_kernel || p == (const void*)qm_policy_fb_pub_kernel) return "policy_fb"; if (p == (const void*)qm_policy_publish_kernel) return "publish"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io"; if (p == (const void*)qm_tick_state_kernel || p == (const void*)qm_tick_pack_kernel) return "tick"; if (p == (const void*)qm_plan_nodes_kernel) return "plan_nodes"; if (p == (const void*)qm_plan_states_kernel) return "plan_states"; if (p == (const void*)qm_plan_footholds_kernel) return "plan_footholds"; if (p == (const void*)qm_episode_tick_kernel || p == (const void*)qm_episode_mpc_kernel || p == (const void*)qm_episode_start_kernel) return "episode";
     return "ls_misc";
   }
   template <class K, class A> void launch(K kernel, int grid, int block, size_t lds, const A& args) {
@@ -130,7 +132,7 @@ struct HipBackend {
 struct qmhip_ctx {
   int device = 0, max_batch = 0, max_nodes = 0, max_ref = 0, max_ev = 0;
   double mb[MB_SIZE], st[ST_SIZE];
-  HipBackend bk; QmMpcPipeline<HipBackend> mpc; QmWbcPipeline<HipBackend> wbc; QmFrontPipeline<HipBackend> front; QmSimPipeline<HipBackend> sim; QmHoqpPipeline<HipBackend> hoqp; QmIoPipeline<HipBackend> io; QmTickPipeline<HipBackend> tick; QmPublishPipeline<HipBackend> pub; QmPlanPipeline<HipBackend> plan;
+  HipBackend bk; QmMpcPipeline<HipBackend> mpc; QmWbcPipeline<HipBackend> wbc; QmFrontPipeline<HipBackend> front; QmSimPipeline<HipBackend> sim; QmHoqpPipeline<HipBackend> hoqp; QmIoPipeline<HipBackend> io; QmTickPipeline<HipBackend> tick; QmPublishPipeline<HipBackend> pub; QmPlanPipeline<HipBackend> plan; QmEpisodePipeline<HipBackend> episode;
   // qmhip_policy_eval_published: a stream, staging and device buffers of its own, serialised among evaluators by eval_mu — an evaluation never takes `mu` below
   std::mutex eval_mu; hipStream_t stream_p = nullptr; char* pe_pin = nullptr; char* pe_dev = nullptr;
   std::recursive_mutex mu;      // serialises the entry points of this context
@@ -139,7 +141,7 @@ struct qmhip_ctx {
   char* tick_pin = nullptr;     // pinned host staging of the control-tick path (qmhip_wbc_step): [inputs of max_batch instances | outputs]
   std::string error; int lastB = 0; bool have_solution = false; int front_B = 0; long sim_ticks = 0;
   hipEvent_t ev_meas = nullptr; bool meas_pending = false;      // streamed step I/O: "the synthetic measured state of the last submitted step has read x0" (the next submit's copy of x0 waits for it on the device)
-  qmhip_ctx() : mpc(bk), wbc(bk), front(bk), sim(bk), hoqp(bk), io(bk), tick(bk), pub(bk), plan(bk) {}
+  qmhip_ctx() : mpc(bk), wbc(bk), front(bk), sim(bk), hoqp(bk), io(bk), tick(bk), pub(bk), plan(bk), episode(bk) {}
   void fail(const std::string& m) { error = m; }
   // getModeSchedule on the device GaitSchedule -> the solver's schedule buffers; from here on its sticky status speaks for the schedule of this batch (until the host supplies one)
   void gait_schedule(int B, double horizon) { front.gait_schedule(mpc.d, B, horizon); mpc.front_status = front.f.gs_status; mpc.front_B = B; }
@@ -261,7 +263,7 @@ int qmhip_create_wbc_context(const qmhip_ctx* c, int max_batch, qmhip_ctx** out)
   return create_common(c->mb, c->st, c->device, max_batch, 3, 1, 1, out, true);      // same model / settings values, own device copies, own streams: nothing mutable is shared
 }
 void qmhip_destroy(qmhip_ctx* c) {
-  if (!c) return; hipSetDevice(c->device); c->bk.sync(); if (c->bk.stream_c) hipStreamSynchronize(c->bk.stream_c); c->io.release(); c->tick.release(); if (c->stream_p) hipStreamSynchronize(c->stream_p); c->pub.release(); c->plan.release(); if (c->pe_pin) hipHostFree(c->pe_pin); if (c->pe_dev) hipFree(c->pe_dev); if (c->stream_p) hipStreamDestroy(c->stream_p); if (c->ev_meas) hipEventDestroy(c->ev_meas); if (c->bk.ev_io_a) { hipEventDestroy(c->bk.ev_io_a); hipEventDestroy(c->bk.ev_io_b); } if (c->dl_dev) hipFree(c->dl_dev); if (c->dl_pin) hipHostFree(c->dl_pin); if (c->tick_pin) hipHostFree(c->tick_pin); c->mpc.release(); c->wbc.release(); c->front.release(); c->sim.release(); c->hoqp.release();
+  if (!c) return; hipSetDevice(c->device); c->bk.sync(); if (c->bk.stream_c) hipStreamSynchronize(c->bk.stream_c); c->io.release(); c->tick.release(); if (c->stream_p) hipStreamSynchronize(c->stream_p); c->pub.release(); c->plan.release(); c->episode.release(); if (c->pe_pin) hipHostFree(c->pe_pin); if (c->pe_dev) hipFree(c->pe_dev); if (c->stream_p) hipStreamDestroy(c->stream_p); if (c->ev_meas) hipEventDestroy(c->ev_meas); if (c->bk.ev_io_a) { hipEventDestroy(c->bk.ev_io_a); hipEventDestroy(c->bk.ev_io_b); } if (c->dl_dev) hipFree(c->dl_dev); if (c->dl_pin) hipHostFree(c->dl_pin); if (c->tick_pin) hipHostFree(c->tick_pin); c->mpc.release(); c->wbc.release(); c->front.release(); c->sim.release(); c->hoqp.release();
   for (auto e : c->bk.pool) hipEventDestroy(e); if (c->bk.ev_order) hipEventDestroy(c->bk.ev_order); hipEventDestroy(c->bk.ev_in); hipEventDestroy(c->bk.ev_wbc); hipStreamDestroy(c->bk.stream); hipStreamDestroy(c->bk.stream_b); if (c->bk.stream_c) hipStreamDestroy(c->bk.stream_c); delete c;
 }
 // the text is copied under the context lock into a per-thread buffer: the pointer stays valid (until this THREAD's next qmhip_last_error) even if another thread's
@@ -692,7 +694,9 @@ int qmhip_sim_reset(qmhip_ctx* c, int B, const double* q, const double* v, const
   if (!c || B <= 0 || B > c->max_batch || !q || !v || !time) { if (c) c->fail("qmhip_sim_reset: bad argument"); return QMHIP_ERR_ARG; }
   hipSetDevice(c->device); c->sim.allocate(c->max_batch); c->sim.reset(B, q, v, time); c->sim_ticks = 0; c->pub.reset_counters();
   c->mpc.solved_B = 0; c->have_solution = false;      // a new episode starts cold, like the reference after "Simulation reset" (no warm start from the previous episode's trajectory)
-  c->sim.step(c->mpc.d.mb, B, 0.0, 0); return c->hipstate();   // rbd / contact of the reset state
+  c->sim.step(c->mpc.d.mb, B, 0.0, 0);   // rbd / contact of the reset state
+  if (c->episode.on) c->episode.start(B, c->sim.s.rbd, c->sim.s.contact);      // episode monitor: a new episode, anchored at the reset state's end-effector pose
+  return c->hipstate();
 }
 int qmhip_sim_set_command(qmhip_ctx* c, int B, const double* pos_des, const double* vel_des, const double* kp, const double* kd, const double* ff) { QM_GUARD(c); QM_NEED_MPC(c);
   if (!c || B <= 0 || B > c->max_batch || !pos_des || !vel_des || !kp || !kd || !ff) { if (c) c->fail("qmhip_sim_set_command: bad argument"); return QMHIP_ERR_ARG; }
@@ -733,9 +737,9 @@ int qmhip_closed_loop_sim(qmhip_ctx* c, int B, int n_ticks, double period, int n
   if (!c->sim.s.Bmax) { c->fail("qmhip_closed_loop_sim: qmhip_sim_reset has not been called"); return QMHIP_ERR_STATE; }
   const bool feedback = c->st[ST_FEEDBACK_POLICY] != 0.0;      // sqp.useFeedbackPolicy: the ticks evaluate the SQP's linear controller at the estimated state
   if (feedback && c->mpc.solver != 0 && c->mpc.solver != 2) { c->fail("qmhip_closed_loop_sim: ST_FEEDBACK_POLICY = 1 needs a multiple-shooting solver slot (ST_SOLVER 0 / 2): the discrete iLQR (1) and the interior-point method (3) hand out no feedback policy"); return QMHIP_ERR_ARG; }
-  hipSetDevice(c->device); c->bk.sync();
+  hipSetDevice(c->device); c->bk.sync(); c->episode.strict = c->st[ST_RICCATI_STRICT] != 0.0 ? 1 : 0;
   qm_closed_loop_sim_ticks(c->bk, c->mpc, c->wbc, c->sim, c->sim_ticks, B, n_ticks, period, n_substeps, mpc_every, horizon, arm_kp, arm_kd, c->sqp_iterations(),
-                           [&]() { if (c->front_B == B) c->gait_schedule(B, horizon); }, feedback);
+                           [&]() { if (c->front_B == B) c->gait_schedule(B, horizon); }, feedback, c->episode.on ? &c->episode : (QmEpisodePipeline<HipBackend>*)nullptr);
   c->lastB = B; c->have_solution = true;
   return c->hipstate();
 }
@@ -749,11 +753,35 @@ int qmhip_closed_loop_sim_pipelined(qmhip_ctx* c, int B, int n_ticks, double per
   if (feedback && c->pub.W == 0) { c->fail("qmhip_closed_loop_sim_pipelined: ST_FEEDBACK_POLICY = 1 is not supported by the pipelined loop without a publish window (the published policy carries no gains); call qmhip_policy_set_publish_window, use qmhip_closed_loop_sim or set it to 0"); return QMHIP_ERR_ARG; }
   if (feedback && c->mpc.solver != 0 && c->mpc.solver != 2) { c->fail("qmhip_closed_loop_sim_pipelined: ST_FEEDBACK_POLICY = 1 needs a multiple-shooting solver slot (ST_SOLVER 0 / 2): the discrete iLQR (1) and the interior-point method (3) hand out no feedback policy"); return QMHIP_ERR_ARG; }
   if (n_ticks % mpc_every || c->sim_ticks % mpc_every) { c->fail("qmhip_closed_loop_sim_pipelined: n_ticks and the tick counter must be multiples of mpc_every"); return QMHIP_ERR_ARG; }
-  hipSetDevice(c->device); c->bk.sync();
+  hipSetDevice(c->device); c->bk.sync(); c->episode.strict = c->st[ST_RICCATI_STRICT] != 0.0 ? 1 : 0;
   qm_closed_loop_sim_pipelined(c->bk, c->mpc, c->wbc, c->sim, c->sim_ticks, B, n_ticks, period, n_substeps, mpc_every, horizon, arm_kp, arm_kd, c->sqp_iterations(),
-                               [&]() { if (c->front_B == B) c->gait_schedule(B, horizon); }, feedback ? &c->pub : (QmPublishPipeline<HipBackend>*)nullptr);
+                               [&]() { if (c->front_B == B) c->gait_schedule(B, horizon); }, feedback ? &c->pub : (QmPublishPipeline<HipBackend>*)nullptr,
+                               c->episode.on ? &c->episode : (QmEpisodePipeline<HipBackend>*)nullptr);
   c->lastB = B; c->have_solution = true; c->bk.sync();
   return c->hipstate();
+}
+
+// ---- episode monitor (k_episode.h, qm_episode_pipeline.h): per-tick statistics and traces of the two loops above; the argument checks are the pipeline's ----
+static int episode_rc(qmhip_ctx* c, int rc) { if (rc != QMHIP_OK) { c->fail(c->episode.why); return rc; } return c->hipstate(); }
+int qmhip_episode_monitor(qmhip_ctx* c, const qmhip_episode_params* p) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c) return QMHIP_ERR_ARG;
+  hipSetDevice(c->device); c->bk.sync(); c->bk.cur = c->bk.stream; c->episode.strict = c->st[ST_RICCATI_STRICT] != 0.0 ? 1 : 0;
+  return episode_rc(c, c->episode.monitor(c->max_batch, (const QmEpisodeParams*)p));
+}
+int qmhip_episode_set_anchor(qmhip_ctx* c, int B, const double* ee_pose) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c) return QMHIP_ERR_ARG; hipSetDevice(c->device); return episode_rc(c, c->episode.set_anchor(B, ee_pose));
+}
+int qmhip_episode_summary(qmhip_ctx* c, int B, struct qmhip_episode_summary* out) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c) return QMHIP_ERR_ARG; hipSetDevice(c->device); return episode_rc(c, c->episode.read_summary(B, out));
+}
+int qmhip_episode_trace(qmhip_ctx* c, int B, int cap, qmhip_episode_sample* out, int32_t* count) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c) return QMHIP_ERR_ARG; hipSetDevice(c->device); return episode_rc(c, c->episode.read_trace(B, cap, out, count));
+}
+int qmhip_episode_fold(qmhip_ctx* c, int B, int tick, double period, const double* time, const double* rbd, const int32_t* contact, const double* force, const int32_t* mode, const double* wbc_out,
+                       const int32_t* qp_status, const int32_t* sim_status, const int32_t* mpc_status) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c) return QMHIP_ERR_ARG; hipSetDevice(c->device);
+  const int rc = c->episode.fold(c->mpc.d.mb, B, tick, period, time, rbd, (const int*)contact, force, (const int*)mode, wbc_out, (const int*)qp_status, (const int*)sim_status, (const int*)mpc_status);
+  c->bk.cur = c->bk.stream; return episode_rc(c, rc);
 }
 
 int qmhip_set_profiling(qmhip_ctx* c, int en) { QM_GUARD(c); if (!c) return QMHIP_ERR_ARG; c->bk.resolve(); c->bk.profiling = (en == 2 || en == 3) ? en : (en != 0); return QMHIP_OK; }

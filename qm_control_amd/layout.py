@@ -7,7 +7,7 @@ _HDR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 DEFINES = {}
 with open(_HDR) as _fh:
     for _line in _fh:
-        _m = re.match(r"#define\s+((?:MB|ST|QM|PR|PT)_\w+)\s+(\d+)\s", _line)
+        _m = re.match(r"#define\s+((?:MB|ST|QM|PR|PT|EP|ES)_\w+)\s+(\d+)\s", _line)
         if _m:
             DEFINES[_m.group(1)] = int(_m.group(2))
             continue
@@ -36,3 +36,20 @@ PLAN_RECORD_FIELDS = [("time", "<f8", 1, 8 * PT_TIME), ("mode", "<i4", 1, 8 * PT
                       ("foot_pos", "<f8", (4, 3), 8 * PT_FOOT_POS), ("foot_vel", "<f8", (4, 3), 8 * PT_FOOT_VEL), ("foot_force", "<f8", (4, 3), 8 * PT_FOOT_FORCE),
                       ("ee_pos", "<f8", 3, 8 * PT_EE_POS), ("ee_quat", "<f8", 4, 8 * PT_EE_QUAT), ("ee_err", "<f8", 6, 8 * PT_EE_ERR), ("cop", "<f8", 3, 8 * PT_COP), ("spare", "<f8", 4, 8 * PT_SPARE)]
 FOOTHOLD_FIELDS = [("time", "<f8", 1, 0), ("leg", "<i4", 1, 8), ("event", "<i4", 1, 12), ("pos", "<f8", 3, 16)]
+
+# struct qmhip_episode_summary / qmhip_episode_sample (include/qmhip_layout.h, the episode monitor), same form, from the EP_* / ES_* word offsets
+_EI = 8 * EP_INTS
+EPISODE_SUMMARY_FIELDS = [("t_first", "<f8", 1, 8 * EP_T_FIRST), ("t_last", "<f8", 1, 8 * EP_T_LAST), ("t_fall", "<f8", 1, 8 * EP_T_FALL), ("min_base_z", "<f8", 1, 8 * EP_MIN_BASE_Z),
+                          ("max_abs_roll", "<f8", 1, 8 * EP_MAX_ROLL), ("max_abs_pitch", "<f8", 1, 8 * EP_MAX_PITCH), ("max_base_speed", "<f8", 1, 8 * EP_MAX_SPEED),
+                          ("max_ee_pos_dev", "<f8", 1, 8 * EP_MAX_EE_POS), ("sum_sq_ee_pos_dev", "<f8", 1, 8 * EP_SUMSQ_EE_POS), ("max_ee_ang_dev", "<f8", 1, 8 * EP_MAX_EE_ANG),
+                          ("max_tau_ratio", "<f8", 1, 8 * EP_MAX_TAU_RATIO), ("max_friction_ratio", "<f8", 1, 8 * EP_MAX_FRICTION), ("max_normal_force", "<f8", 1, 8 * EP_MAX_NORMAL),
+                          ("joint_work", "<f8", 1, 8 * EP_JOINT_WORK), ("spare", "<f8", 2, 8 * EP_SPARE),
+                          ("ticks", "<i4", 1, _EI + 4 * EP_I_TICKS), ("fall_tick", "<i4", 1, _EI + 4 * EP_I_FALL_TICK), ("fall_cause", "<i4", 1, _EI + 4 * EP_I_FALL_CAUSE),
+                          ("sim_bad_ticks", "<i4", 1, _EI + 4 * EP_I_SIM_BAD), ("mpc_calls", "<i4", 1, _EI + 4 * EP_I_MPC_CALLS), ("mpc_fail_calls", "<i4", 1, _EI + 4 * EP_I_MPC_FAILS),
+                          ("mpc_warn_or", "<i4", 1, _EI + 4 * EP_I_MPC_WARN_OR), ("mpc_last_fail", "<i4", 1, _EI + 4 * EP_I_MPC_LAST_FAIL),
+                          ("mpc_first_fail_tick", "<i4", 1, _EI + 4 * EP_I_MPC_FIRST_FAIL), ("reserved", "<i4", 1, _EI + 4 * EP_I_RESERVED), ("wbc_bad_ticks", "<i4", 3, _EI + 4 * EP_I_WBC_BAD),
+                          ("airborne_ticks", "<i4", 1, _EI + 4 * EP_I_AIRBORNE), ("contact_mismatch_ticks", "<i4", 4, _EI + 4 * EP_I_MISMATCH), ("touchdowns", "<i4", 4, _EI + 4 * EP_I_TOUCHDOWN),
+                          ("tau_over_ticks", "<i4", 1, _EI + 4 * EP_I_TAU_OVER), ("ispare", "<i4", 9, _EI + 4 * EP_I_SPARE)]
+_SI = 8 * ES_INTS
+EPISODE_SAMPLE_FIELDS = [("time", "<f8", 1, 8 * ES_TIME), ("rbd", "<f8", 55, 8 * ES_RBD), ("force_z", "<f8", 4, 8 * ES_FORCE_Z), ("tick", "<i4", 1, _SI), ("mode", "<i4", 1, _SI + 4),
+                         ("contact_mask", "<i4", 1, _SI + 8), ("mpc_status", "<i4", 1, _SI + 12), ("qp_status", "<i4", 3, _SI + 16), ("sim_status", "<i4", 1, _SI + 28)]
