@@ -90,6 +90,19 @@ class QmhipSolver final : public ocs2::SolverBase {
   const double* lastPerformance() const { return perf_; }             // baseline{merit,cost,dynSSE,eqSSE}, after{...}, alpha, armijo
   void setFeedbackPolicy(bool on) { feedback_ = on; }                 // sqp::Settings::useFeedbackPolicy (task.info:89): hand out a LinearController instead of a FeedforwardController
   void setStreamedIo(bool on) { streamed_ = on; }                     // false: warm calls go through qmhip_mpc_set_initial + qmhip_mpc_solve_resident_warm + qmhip_mpc_download again
+  // MPC_MRT_Interface::rolloutPolicy(currentTime, currentState, timeStep, mpcState, mpcInput, mode) [upstream, recalled] — the seam QMController.cpp:311 opens with
+  // initRollout(&qmInterface_->getRollout()) — on the device (qmhip_policy_rollout, include/qmhip.h): the model integrated from the MEASURED state over timeStep under the
+  // policy of the last solve (the linear controller with setFeedbackPolicy(true), the feed-forward policy otherwise), Heun steps of sqp.dt with the input held, NOT the
+  // reference's adaptive ODE45 rollout.  published: read the active publication (qmhip_policy_publish) instead — safe from the control thread while mpcThread_ solves
+  void rolloutPolicy(ocs2::scalar_t currentTime, const ocs2::vector_t& currentState, ocs2::scalar_t timeStep, ocs2::vector_t& mpcState, ocs2::vector_t& mpcInput, size_t& mode,
+                     ocs2::scalar_t maxStep = 0.015, bool published = false, struct qmhip_rollout_summary* summary = nullptr) const {
+    if (currentState.size() != QM_NX) throw std::runtime_error("[QmhipSolver] state dimension must be 30");
+    const double t0 = currentTime, t1 = currentTime + timeStep; int32_t md = 0; const int32_t inst = 0;
+    qmhip_rollout_params p; p.max_step = maxStep; p.max_steps = 4096; p.source = published ? 1 : 0; p.feedback = feedback_ ? 1 : 0; p.trace_cap = 0;
+    mpcState.resize(QM_NX); mpcInput.resize(QM_NU);
+    check(qmhip_policy_rollout(ctx_, 1, &inst, &t0, currentState.data(), &t1, &p, mpcState.data(), mpcInput.data(), &md, summary, nullptr, nullptr, nullptr), "qmhip_policy_rollout");
+    mode = (size_t)md;
+  }
 
  private:
   void runImpl(ocs2::scalar_t initTime, const ocs2::vector_t& initState, ocs2::scalar_t finalTime) override {

@@ -48,6 +48,7 @@ struct vector_t {                               // Eigen::VectorXd stand-in
   vector_t() = default;
   explicit vector_t(long n) : v((size_t)n, 0.0) {}
   long size() const { return (long)v.size(); }
+  void resize(long n) { v.resize((size_t)n); }   // (QmhipSolver::rolloutPolicy sizes its two outputs)
   double* data() { return v.data(); }
   const double* data() const { return v.data(); }
   double& operator()(long i) { return v[(size_t)i]; }

@@ -324,6 +324,35 @@ int qmhip_plan_footholds(qmhip_ctx* ctx, int B, int cap, qmhip_foothold* out /*[
 int qmhip_task_space_eval(qmhip_ctx* ctx, int R, const double* x /*[R][30]*/, const double* u /*[R][30] or NULL*/, const int32_t* mode /*[R]*/,
                           const double* ee_ref /*[R][7] pos + quat xyzw, or NULL*/, qmhip_plan_record* rec /*[R]*/);
 
+/* ---- policy rollout: MPC_MRT_Interface::rolloutPolicy(currentTime, currentState, timeStep, mpcState, mpcInput, mode) [upstream, recalled] — the rollout the reference
+ *      initialises at qm_controllers/src/QMController.cpp:311 (a TimeTriggeredRollout over QMDynamicsAD, qm_interface/src/QMInterface.cpp:73,136-137) — batched: the
+ *      model integrated forward from a state that is NOT the plan's, under the active policy, with a summary.  R rows, each an instance of the last solve (or of the active
+ *      publication) with a start (t0, x0) and an absolute final time t_end >= t0; one wavefront per row, many rows per instance.
+ *      Evaluation points k = 0 .. K: t_0 = t0, t_{k+1} = min(t_k + max_step, e, t_end) with e the first event of the instance's schedule strictly behind t_k, accumulated
+ *        exactly like this (a rollout continued from a returned t_k repeats the same doubles); it ends at t_end or after max_steps steps (QM_ROLLOUT_MAX_STEPS).  The query
+ *        time is t_k, or t_k + weakEpsilon when t_k equals an event time bit for bit: a step that starts on an event sees the mode and the PostEvent node behind it.
+ *      At every point, the last included: x_des, u_ff = the feed-forward policy, mode_k = the schedule's mode, u_k = u_ff (feedback 0) or what qmhip_policy_eval_feedback
+ *        (source 0) / qmhip_policy_eval_published (source 1, with its feed-forward fall-back outside the window) return at (time, x_k).  Times outside the plan's grid
+ *        clamp as there (QM_ROLLOUT_OUTSIDE).  Then x_{k+1} = x_k + h/2 (f(x_k, u_k) + f(x_k + h f(x_k, u_k), u_k)): u_k HELD over the step, the transcription's Heun rule —
+ *        the discrete model the Riccati gains belong to, hence max_step = sqp.dt by default — NOT upstream's adaptive ODE45.  A non-finite x_{k+1} ends the rollout at
+ *        point k (QM_ROLLOUT_NONFINITE).
+ *      Out: x_end = x_K, u_end = u_K, mode_end = mode_K (what rolloutPolicy returns); per row a struct qmhip_rollout_summary of include/qmhip_layout.h, folded over the K + 1
+ *        points — largest deviation from the plan per state block, largest feedback term, smallest friction-cone margin and normal force over stance feet (+ infinity
+ *        without one), largest force on a swing foot, steps, steps that ended on an event, uncovered points, flags; optionally a trace of qmhip_rollout_sample, one per
+ *        point k < trace_cap, row-major [R][trace_cap]: count[r] = K + 1 keeps counting behind the cap (the rule of qmhip_plan_footholds), slots at or behind it are left alone.
+ *      source 0 reads the last solve's stage records under the context lock on the MPC stream: valid as qmhip_policy_eval_feedback is.  source 1 reads the ACTIVE
+ *        publication on the published policy's stream under the publication mutex, never the context lock — beside a running solve, from another thread — and returns its
+ *        sequence number in *seq.  Row buffers grow on demand and are kept, per source.
+ *      QMHIP_ERR_STATE: no solve yet (or after an upload / reset / solver switch), a streamed step or tick in flight (source 0); no publication, feedback = 1 on a publication
+ *        without gains (source 1); a WBC-only context.  QMHIP_ERR_ARG: R < 1; an inst entry outside the batch of the solve / publication (inst NULL: R beyond it); a NULL
+ *        among t0, x0, t_end, p, x_end, u_end, mode_end; max_step not a positive finite number; max_steps < 1; source / feedback other than 0 / 1; trace_cap < 0, or > 0
+ *        with trace NULL; a t0 / t_end that is not finite, or t_end < t0; feedback = 1 with ST_SOLVER 1 or 3.  An error writes to none of the caller's arrays. */
+typedef struct qmhip_rollout_params { double max_step; int32_t max_steps, source, feedback, trace_cap; } qmhip_rollout_params;
+int qmhip_policy_rollout(qmhip_ctx* ctx, int R, const int32_t* inst /*[R] or NULL: row r = instance r*/, const double* t0 /*[R]*/, const double* x0 /*[R][30]*/,
+                         const double* t_end /*[R]*/, const qmhip_rollout_params* p, double* x_end /*[R][30]*/, double* u_end /*[R][30]*/, int32_t* mode_end /*[R]*/,
+                         struct qmhip_rollout_summary* summary /*[R] or NULL*/, qmhip_rollout_sample* trace /*[R][trace_cap] or NULL*/, int32_t* count /*[R] or NULL*/,
+                         int64_t* seq /*out or NULL; source 1*/);
+
 /* ---- batched rigid-body plant: stands where Gazebo + qm_gazebo::QMHWSim stand in the reference.
  *      sim_set_command = HybridJointHandle::setCommand as QMController::updateControlLaw issues it (qm_controllers/src/QMController.cpp:177-190):
  *        per joint posDes, velDes, kp, kd, ff in the reference's joint order (LF, LH, RF, RH, arm).

@@ -297,8 +297,51 @@ typedef struct qmhip_episode_sample {
   double time, rbd[55], force_z[4];
   int32_t tick, mode, contact_mask, mpc_status, qp_status[3], sim_status;
 } qmhip_episode_sample;
+
+/* policy rollout (qmhip.h, "policy rollout"): per-row summary and trace sample of qmhip_policy_rollout, written on the device by qm_policy_rollout_kernel
+   (csrc/kernels/k_rollout.h).  QM_RS_* are offsets in 8-byte WORDS of struct qmhip_rollout_summary (16 words: 12 doubles, then 8 int32, two per word; QM_RS_I_* are
+   indices of those int32), QM_RT_* offsets in 8-byte words of qmhip_rollout_sample (64 words: 61 doubles, then 6 int32).  Folded over all K + 1 evaluation points */
+#define QM_RS_T_END       0    /* time reached                                                              */
+#define QM_RS_MAX_DEV     1    /* [4] inf-norm of x_k - x_des(tau_k): momentum / base pose / leg joints / arm joints */
+#define QM_RS_MAX_FB      5    /* [2] inf-norm of u_k - u_ff(tau_k): contact forces / joint velocities      */
+#define QM_RS_MIN_CONE    7    /* min over stance feet of ST_FRIC_COEF F_z - sqrt(F_x^2 + F_y^2); + infinity without a stance foot */
+#define QM_RS_MIN_FZ      8    /* min over stance feet of F_z; + infinity without a stance foot             */
+#define QM_RS_MAX_SWING   9    /* max over swing feet of |F|_inf                                            */
+#define QM_RS_SPARE       10   /* [2] zero                                                                  */
+#define QM_RS_INTS        12   /* first word of the int32 part                                              */
+#define QM_RS_I_STEPS     0    /* steps taken (K)                                                           */
+#define QM_RS_I_EVENTS    1    /* steps that ended on an event of the schedule                              */
+#define QM_RS_I_UNCOVERED 2    /* source 1: evaluation points outside the publication window                */
+#define QM_RS_I_FLAGS     3    /* QM_ROLLOUT_* bits                                                         */
+#define QM_RS_I_SPARE     4    /* [4] zero                                                                  */
+#define QM_RS_WORDS 16
+#define QM_RS_BYTES 128
+#define QM_ROLLOUT_MAX_STEPS 1 /* max_steps reached before t_end                                            */
+#define QM_ROLLOUT_NONFINITE 2 /* a step gave a non-finite state: x_end is the last finite one              */
+#define QM_ROLLOUT_OUTSIDE   4 /* a query time outside the plan's grid (clamped as the policy entry points clamp) */
+/* (a struct TAG, no typedef, like qmhip_episode_summary) */
+struct qmhip_rollout_summary {
+  double t_end, max_dev[4], max_fb[2], min_cone, min_fz, max_swing_force, spare[2];
+  int32_t steps, events, uncovered, flags, ispare[4];
+};
+#define QM_RT_TIME  0    /* t_k                                                                             */
+#define QM_RT_X     1    /* [30] x_k                                                                        */
+#define QM_RT_U     31   /* [30] u_k                                                                        */
+#define QM_RT_INTS  61   /* int32: mode_k, covered (source 0: always 1), then four zeros                    */
+#define QM_RT_WORDS 64
+#define QM_RT_BYTES 512
+typedef struct qmhip_rollout_sample {
+  double t, x[30], u[30];
+  int32_t mode, covered, ispare[4];
+} qmhip_rollout_sample;
 #ifdef __cplusplus
 #include <stddef.h>
+static_assert(sizeof(struct qmhip_rollout_summary) == QM_RS_BYTES && QM_RS_WORDS * 8 == QM_RS_BYTES && offsetof(struct qmhip_rollout_summary, max_dev) == 8 * QM_RS_MAX_DEV &&
+              offsetof(struct qmhip_rollout_summary, max_fb) == 8 * QM_RS_MAX_FB && offsetof(struct qmhip_rollout_summary, min_cone) == 8 * QM_RS_MIN_CONE && offsetof(struct qmhip_rollout_summary, min_fz) == 8 * QM_RS_MIN_FZ &&
+              offsetof(struct qmhip_rollout_summary, max_swing_force) == 8 * QM_RS_MAX_SWING && offsetof(struct qmhip_rollout_summary, spare) == 8 * QM_RS_SPARE && offsetof(struct qmhip_rollout_summary, steps) == 8 * QM_RS_INTS &&
+              offsetof(struct qmhip_rollout_summary, flags) == 8 * QM_RS_INTS + 4 * QM_RS_I_FLAGS && offsetof(struct qmhip_rollout_summary, ispare) == 8 * QM_RS_INTS + 4 * QM_RS_I_SPARE, "QM_RS_* are the word / int32 offsets of qmhip_rollout_summary (16 eight-byte words)");
+static_assert(sizeof(qmhip_rollout_sample) == QM_RT_BYTES && QM_RT_WORDS * 8 == QM_RT_BYTES && offsetof(qmhip_rollout_sample, x) == 8 * QM_RT_X && offsetof(qmhip_rollout_sample, u) == 8 * QM_RT_U &&
+              offsetof(qmhip_rollout_sample, mode) == 8 * QM_RT_INTS && offsetof(qmhip_rollout_sample, covered) == 8 * QM_RT_INTS + 4, "QM_RT_* are the word offsets of qmhip_rollout_sample (64 eight-byte words)");
 static_assert(sizeof(struct qmhip_episode_summary) == QM_EP_BYTES && QM_EP_WORDS * 8 == QM_EP_BYTES && 8 * EP_INTS + 4 * (EP_I_SPARE + 9) == QM_EP_BYTES, "qmhip_episode_summary is 32 eight-byte words");
 static_assert(offsetof(struct qmhip_episode_summary, t_fall) == 8 * EP_T_FALL && offsetof(struct qmhip_episode_summary, min_base_z) == 8 * EP_MIN_BASE_Z && offsetof(struct qmhip_episode_summary, max_ee_pos_dev) == 8 * EP_MAX_EE_POS &&
               offsetof(struct qmhip_episode_summary, joint_work) == 8 * EP_JOINT_WORK && offsetof(struct qmhip_episode_summary, spare) == 8 * EP_SPARE && offsetof(struct qmhip_episode_summary, ticks) == 8 * EP_INTS &&

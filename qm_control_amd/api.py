@@ -27,7 +27,7 @@ EXPORTS = ["qmhip_create", "qmhip_create_from_blobs", "qmhip_create_wbc_context"
            "qmhip_gait_set_templates", "qmhip_gait_reset", "qmhip_gait_insert_template", "qmhip_gait_update_resident", "qmhip_gait_download", "qmhip_schedule_download",
            "qmhip_target_reset", "qmhip_target_from_command", "qmhip_target_download",
            "qmhip_step_submit", "qmhip_step_collect", "qmhip_step_in_flight",
-           "qmhip_plan_task_space", "qmhip_plan_footholds", "qmhip_task_space_eval",
+           "qmhip_plan_task_space", "qmhip_plan_footholds", "qmhip_task_space_eval", "qmhip_policy_rollout",
            "qmhip_episode_monitor", "qmhip_episode_set_anchor", "qmhip_episode_summary", "qmhip_episode_trace", "qmhip_episode_fold",
            "qmhip_tick_reset", "qmhip_tick_submit", "qmhip_tick_collect", "qmhip_observe", "qmhip_sim_get_rbd",
            "qmhip_sim_set_params", "qmhip_sim_set_controller", "qmhip_sim_reset", "qmhip_sim_set_command", "qmhip_sim_step", "qmhip_sim_get_state", "qmhip_closed_loop_sim", "qmhip_closed_loop_sim_pipelined"]
@@ -48,7 +48,15 @@ FOOTHOLD = _rec_dtype(L.FOOTHOLD_FIELDS, L.QM_FOOTHOLD_BYTES)
 # struct qmhip_episode_summary: one 256-byte record per instance of a monitored episode; struct qmhip_episode_sample: one 512-byte raw sample (QMHWSim.monitor)
 EPISODE_SUMMARY = _rec_dtype(L.EPISODE_SUMMARY_FIELDS, L.QM_EP_BYTES)
 EPISODE_SAMPLE = _rec_dtype(L.EPISODE_SAMPLE_FIELDS, L.QM_ES_BYTES)
+# struct qmhip_rollout_summary: one 128-byte record per row of a policy rollout; qmhip_rollout_sample: one 512-byte trace sample per evaluation point (SqpMpc.rollout_policy)
+ROLLOUT_SUMMARY = _rec_dtype(L.ROLLOUT_SUMMARY_FIELDS, L.QM_RS_BYTES)
+ROLLOUT_SAMPLE = _rec_dtype(L.ROLLOUT_SAMPLE_FIELDS, L.QM_RT_BYTES)
+ROLLOUT_MAX_STEPS, ROLLOUT_NONFINITE, ROLLOUT_OUTSIDE = L.QM_ROLLOUT_MAX_STEPS, L.QM_ROLLOUT_NONFINITE, L.QM_ROLLOUT_OUTSIDE
 FALL_HEIGHT, FALL_ROLL, FALL_PITCH, FALL_NONFINITE = L.QM_FALL_HEIGHT, L.QM_FALL_ROLL, L.QM_FALL_PITCH, L.QM_FALL_NONFINITE
+
+
+class _RolloutParams(C.Structure):
+    _fields_ = [("max_step", C.c_double), ("max_steps", C.c_int32), ("source", C.c_int32), ("feedback", C.c_int32), ("trace_cap", C.c_int32)]
 
 
 class _EpisodeParams(C.Structure):
@@ -374,6 +382,36 @@ class SqpMpc:
         B = self.B; fh = np.zeros((B, int(cap)), FOOTHOLD); cnt = np.zeros(B, np.int32)
         self.itf._check(self.lib.qmhip_plan_footholds(self.itf.h, B, int(cap), fh.ctypes.data_as(C.c_void_p) if cap else None, _pi(cnt)), "qmhip_plan_footholds")
         return fh, cnt
+
+    def rollout_policy(self, t, x, t_end, inst=None, *, max_step=None, max_steps=4096, feedback=True, source="solve", trace=0):
+        """MPC_MRT_Interface::rolloutPolicy, batched (qmhip_policy_rollout): R rows — start times t [R], start states x [R][30], absolute final times t_end [R] (or one for
+        all rows), inst [R] the instance of the last solve / the active publication a row rolls out (None: row r = instance r) — integrated with the transcription's Heun
+        rule at steps of at most max_step (None: sqp.dt, the step the gains belong to) that also end on the schedule's events, the input held over a step.  feedback:
+        the SQP's linear controller at the rolled state (True) or the feed-forward policy; source "solve": the last solve (the validity window of evaluate_policy(t, x)),
+        "published": the active publication, safe beside a running solve.  trace: samples to keep per row.
+        Returns dict(x, u, mode = the end point's state, input, mode; summary [R] of dtype ROLLOUT_SUMMARY), with a trace also trace [R][trace] of dtype ROLLOUT_SAMPLE
+        and count [R] (evaluation points; the first min(count, trace) samples of a row are written), for "published" also seq"""
+        t = np.atleast_1d(_f(t)); R = t.shape[0]; xs = _f(np.atleast_2d(x), (R, 30)); te = _f(np.broadcast_to(np.asarray(t_end, float), (R,)))
+        ins = None if inst is None else np.ascontiguousarray(np.broadcast_to(np.asarray(inst, np.int32), (R,)), dtype=np.int32)
+        if source not in ("solve", "published"):
+            raise ValueError("source is 'solve' or 'published'")
+        step = self.itf.settings_blob[L.ST_IPM_DT if self.itf.settings_blob[L.ST_SOLVER] >= 2.0 else L.ST_SQP_DT] if max_step is None else max_step
+        p = _RolloutParams(float(step), int(max_steps), 1 if source == "published" else 0, int(bool(feedback)), int(trace))
+        xe = np.zeros((R, 30)); ue = np.zeros((R, 30)); mode = np.zeros(R, np.int32); sm = np.zeros(R, ROLLOUT_SUMMARY); cnt = np.zeros(R, np.int32); seq = C.c_int64(0)
+        tr = np.zeros((R, int(trace)), ROLLOUT_SAMPLE) if trace else None
+        self.itf._check(self.lib.qmhip_policy_rollout(self.itf.h, R, _pi(ins), _p(t), _p(xs), _p(te), C.byref(p), _p(xe), _p(ue), _pi(mode), sm.ctypes.data_as(C.c_void_p),
+                                                      tr.ctypes.data_as(C.c_void_p) if trace else None, _pi(cnt), C.byref(seq)), "qmhip_policy_rollout")
+        out = dict(x=xe, u=ue, mode=mode, summary=sm)
+        if trace: out.update(trace=tr, count=cnt)
+        if source == "published": out["seq"] = seq.value
+        return out
+
+    def rolloutPolicy(self, currentTime, currentState, timeStep):
+        """MPC_MRT_Interface::rolloutPolicy(currentTime, currentState, timeStep, mpcState, mpcInput, mode) for the batch of the last solve: instance b rolled from
+        (currentTime[b], currentState[b]) over timeStep under the policy ST_FEEDBACK_POLICY selects.  Returns (mpcState, mpcInput, mode)"""
+        t = _f(np.broadcast_to(np.asarray(currentTime, float), (self.B,)))
+        r = self.rollout_policy(t, _f(currentState, (self.B, 30)), t + float(timeStep), feedback=self.itf.settings_blob[L.ST_FEEDBACK_POLICY] != 0.0)
+        return r["x"], r["u"], r["mode"]
 
     def feedback(self):
         """the linear controller of the last solve as ocs2::LinearController holds it (qmhip_mpc_download_feedback): (gain [B][max_nodes][30][30], uff [B][max_nodes][30]) on the

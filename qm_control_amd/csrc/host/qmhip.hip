@@ -22,6 +22,8 @@
 #include "qm_publish_pipeline.h"
 #include "qm_plan_pipeline.h"
 #include "qm_episode_pipeline.h"
+#include "qm_rollout_pipeline.h"
+static_assert(QM_RO_OK == QMHIP_OK && QM_RO_ERR_ARG == QMHIP_ERR_ARG && QM_RO_ERR_STATE == QMHIP_ERR_STATE, "qm_rollout_pipeline.h restates the error codes of qmhip.h");
 static_assert(QM_EP_OK == QMHIP_OK && QM_EP_ERR_ARG == QMHIP_ERR_ARG && QM_EP_ERR_STATE == QMHIP_ERR_STATE && sizeof(QmEpisodeParams) == sizeof(qmhip_episode_params), "qm_episode_pipeline.h restates the error codes and the parameter struct of qmhip.h");
 
 static thread_local std::string g_create_error;      // per calling thread: qmhip_last_error(NULL) is the error of THIS thread's last failed create
@@ -51,7 +53,7 @@ struct HipBackend {
     const void* p = (const void*)k;
     if (p == (const void*)qm_grid_kernel || p == (const void*)qm_grid_nodes_kernel || p == (const void*)qm_save_grid_kernel || p == (const void*)qm_advance_kernel) return "grid"; if (p == (const void*)qm_lq_kernel || p == (const void*)qm_lq_dbg_kernel || p == (const void*)qm_lq_ipm_kernel) return "lq"; if (p == (const void*)qm_lq_m18_kernel) return "lq_m18"; if (p == (const void*)qm_lq_kin_kernel) return "lq_kin"; if (p == (const void*)qm_riccati_kernel || p == (const void*)qm_riccati_prof_kernel) return "riccati";
     if (p == (const void*)qm_ls_eval_kernel || p == (const void*)qm_ls_eval_dense_kernel || p == (const void*)qm_ls_eval_ipm_kernel) return "ls_eval";
-    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel) return "rollout"; if (p == (const void*)qm_sim_kernel) return "sim"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_policy_fb_kernel || p == (const void*)qm_policy_fb_pub_kernel) return "policy_fb"; if (p == (const void*)qm_policy_publish_kernel) return "publish"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io"; if (p == (const void*)qm_tick_state_kernel || p == (const void*)qm_tick_pack_kernel) return "tick"; if (p == (const void*)qm_plan_nodes_kernel) return "plan_nodes"; if (p == (const void*)qm_plan_states_kernel) return "plan_states"; if (p == (const void*)qm_plan_footholds_kernel) return "plan_footholds"; if (p == (const void*)qm_episode_tick_kernel || p == (const void*)qm_episode_mpc_kernel || p == (const void*)qm_episode_start_kernel) return "episode";
+    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel || p == (const void*)(QmPolicyRolloutFn)qm_policy_rollout_kernel<QmFbStageView, SR_SIZE, false> || p == (const void*)(QmPolicyRolloutFn)qm_policy_rollout_kernel<QmFbPubView, PR_SIZE, true>) return "rollout"; if (p == (const void*)qm_sim_kernel) return "sim"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_policy_fb_kernel || p == (const void*)qm_policy_fb_pub_kernel) return "policy_fb"; if (p == (const void*)qm_policy_publish_kernel) return "publish"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io"; if (p == (const void*)qm_tick_state_kernel || p == (const void*)qm_tick_pack_kernel) return "tick"; if (p == (const void*)qm_plan_nodes_kernel) return "plan_nodes"; if (p == (const void*)qm_plan_states_kernel) return "plan_states"; if (p == (const void*)qm_plan_footholds_kernel) return "plan_footholds"; if (p == (const void*)qm_episode_tick_kernel || p == (const void*)qm_episode_mpc_kernel || p == (const void*)qm_episode_start_kernel) return "episode";
     return "ls_misc";
   }
   template <class K, class A> void launch(K kernel, int grid, int block, size_t lds, const A& args) {
@@ -129,12 +131,40 @@ struct HipBackend {
   void wbc_end() { check(hipEventRecord(ev_wbc, stream_b), "hipEventRecord"); cur = stream; wbc_pending = true; }
 };
 
+// the two queues of the policy rollout (qm_rollout_pipeline.h).  Source 0: the MPC stream through the backend (profiling spans, the backend's error word), under the context
+// lock.  Source 1: the published policy's stream with raw calls and an error word of its own: it runs under the publication mutex and must not touch the backend's state
+struct RolloutQueueMpc {
+  HipBackend& bk;
+  void* alloc(size_t n) { return bk.alloc(n); }
+  void free(void* p) { bk.free(p); }
+  void* alloc_pinned(size_t n) { return bk.alloc_pinned(n); }
+  void free_pinned(void* p) { bk.free_pinned(p); }
+  void ro_in(void* d, const void* s, size_t n) { bk.check(hipMemcpyAsync(d, s, n, hipMemcpyHostToDevice, bk.stream), "H2D"); }
+  template <class K, class A> void launch(K kernel, int grid, int block, size_t lds, const A& args) { bk.cur = bk.stream; bk.launch(kernel, grid, block, lds, args); }
+  void ro_out(void* d, const void* s, size_t n) { bk.check(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToHost, bk.stream), "D2H"); }
+  void ro_wait() { bk.check(hipStreamSynchronize(bk.stream), "sync"); }
+};
+struct RolloutQueuePub {
+  hipStream_t* sp; std::string error;
+  void check(hipError_t e, const char* what) { if (e != hipSuccess && error.empty()) error = std::string(what) + ": " + hipGetErrorString(e); }
+  void* alloc(size_t n) { void* p = nullptr; check(hipMalloc(&p, n ? n : 8), "hipMalloc"); return p; }
+  void free(void* p) { hipFree(p); }
+  void* alloc_pinned(size_t n) { void* h = nullptr; check(hipHostMalloc(&h, n ? n : 8, hipHostMallocDefault), "hipHostMalloc"); return h; }
+  void free_pinned(void* p) { hipHostFree(p); }
+  void ro_in(void* d, const void* s, size_t n) { check(hipMemcpyAsync(d, s, n, hipMemcpyHostToDevice, *sp), "H2D"); }
+  template <class K, class A> void launch(K kernel, int grid, int block, size_t lds, const A& args) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, *sp, args); check(hipGetLastError(), "kernel launch"); }
+  void ro_out(void* d, const void* s, size_t n) { check(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToHost, *sp), "D2H"); }
+  void ro_wait() { check(hipStreamSynchronize(*sp), "sync"); }
+};
+
 struct qmhip_ctx {
   int device = 0, max_batch = 0, max_nodes = 0, max_ref = 0, max_ev = 0;
   double mb[MB_SIZE], st[ST_SIZE];
   HipBackend bk; QmMpcPipeline<HipBackend> mpc; QmWbcPipeline<HipBackend> wbc; QmFrontPipeline<HipBackend> front; QmSimPipeline<HipBackend> sim; QmHoqpPipeline<HipBackend> hoqp; QmIoPipeline<HipBackend> io; QmTickPipeline<HipBackend> tick; QmPublishPipeline<HipBackend> pub; QmPlanPipeline<HipBackend> plan; QmEpisodePipeline<HipBackend> episode;
   // qmhip_policy_eval_published: a stream, staging and device buffers of its own, serialised among evaluators by eval_mu — an evaluation never takes `mu` below
   std::mutex eval_mu; hipStream_t stream_p = nullptr; char* pe_pin = nullptr; char* pe_dev = nullptr;
+  // qmhip_policy_rollout: source 0 on the MPC stream under `mu`, source 1 on stream_p under eval_mu — a queue and row buffers each (qm_rollout_pipeline.h)
+  RolloutQueueMpc ro_q{bk}; RolloutQueuePub ro_qp{&stream_p, std::string()}; QmRolloutPipeline<RolloutQueueMpc> rollout{ro_q}; QmRolloutPipeline<RolloutQueuePub> rollout_p{ro_qp};
   std::recursive_mutex mu;      // serialises the entry points of this context
   bool wbc_only = false;        // created by qmhip_create_wbc_context: carries the model + the WBC buffers, no horizon buffers
   void* dl_dev = nullptr; void* dl_pin = nullptr; size_t dl_cap = 0;      // staging of qmhip_mpc_download (device transpose buffer + its pinned host mirror), allocated on first use
@@ -263,7 +293,7 @@ int qmhip_create_wbc_context(const qmhip_ctx* c, int max_batch, qmhip_ctx** out)
   return create_common(c->mb, c->st, c->device, max_batch, 3, 1, 1, out, true);      // same model / settings values, own device copies, own streams: nothing mutable is shared
 }
 void qmhip_destroy(qmhip_ctx* c) {
-  if (!c) return; hipSetDevice(c->device); c->bk.sync(); if (c->bk.stream_c) hipStreamSynchronize(c->bk.stream_c); c->io.release(); c->tick.release(); if (c->stream_p) hipStreamSynchronize(c->stream_p); c->pub.release(); c->plan.release(); c->episode.release(); if (c->pe_pin) hipHostFree(c->pe_pin); if (c->pe_dev) hipFree(c->pe_dev); if (c->stream_p) hipStreamDestroy(c->stream_p); if (c->ev_meas) hipEventDestroy(c->ev_meas); if (c->bk.ev_io_a) { hipEventDestroy(c->bk.ev_io_a); hipEventDestroy(c->bk.ev_io_b); } if (c->dl_dev) hipFree(c->dl_dev); if (c->dl_pin) hipHostFree(c->dl_pin); if (c->tick_pin) hipHostFree(c->tick_pin); c->mpc.release(); c->wbc.release(); c->front.release(); c->sim.release(); c->hoqp.release();
+  if (!c) return; hipSetDevice(c->device); c->bk.sync(); if (c->bk.stream_c) hipStreamSynchronize(c->bk.stream_c); c->io.release(); c->tick.release(); if (c->stream_p) hipStreamSynchronize(c->stream_p); c->pub.release(); c->plan.release(); c->episode.release(); c->rollout.release(); c->rollout_p.release(); if (c->pe_pin) hipHostFree(c->pe_pin); if (c->pe_dev) hipFree(c->pe_dev); if (c->stream_p) hipStreamDestroy(c->stream_p); if (c->ev_meas) hipEventDestroy(c->ev_meas); if (c->bk.ev_io_a) { hipEventDestroy(c->bk.ev_io_a); hipEventDestroy(c->bk.ev_io_b); } if (c->dl_dev) hipFree(c->dl_dev); if (c->dl_pin) hipHostFree(c->dl_pin); if (c->tick_pin) hipHostFree(c->tick_pin); c->mpc.release(); c->wbc.release(); c->front.release(); c->sim.release(); c->hoqp.release();
   for (auto e : c->bk.pool) hipEventDestroy(e); if (c->bk.ev_order) hipEventDestroy(c->bk.ev_order); hipEventDestroy(c->bk.ev_in); hipEventDestroy(c->bk.ev_wbc); hipStreamDestroy(c->bk.stream); hipStreamDestroy(c->bk.stream_b); if (c->bk.stream_c) hipStreamDestroy(c->bk.stream_c); delete c;
 }
 // the text is copied under the context lock into a per-thread buffer: the pointer stays valid (until this THREAD's next qmhip_last_error) even if another thread's
@@ -635,6 +665,55 @@ int qmhip_plan_footholds(qmhip_ctx* c, int B, int cap, qmhip_foothold* out, int3
 int qmhip_task_space_eval(qmhip_ctx* c, int R, const double* x, const double* u, const int32_t* mode, const double* ee_ref, qmhip_plan_record* rec) { QM_GUARD(c); QM_NEED_MPC(c);
   if (!c || R <= 0 || (long long)R > (long long)c->max_batch * c->max_nodes || !x || !mode || !rec) { if (c) c->fail("qmhip_task_space_eval: bad argument (1 <= R <= max_batch * max_nodes; x, mode and rec required)"); return QMHIP_ERR_ARG; }
   hipSetDevice(c->device); c->plan.eval(c->mpc.d.mb, R, x, u, mode, ee_ref, rec); return c->hipstate();
+}
+
+// ---- policy rollout (k_rollout.h, qm_rollout_pipeline.h): MPC_MRT_Interface::rolloutPolicy [upstream, recalled], batched; the rollout QMController.cpp:311 initialises ----
+static_assert(sizeof(QmRolloutParams) == sizeof(qmhip_rollout_params) && offsetof(QmRolloutParams, trace_cap) == offsetof(qmhip_rollout_params, trace_cap), "qm_rollout_pipeline.h restates the parameter struct of qmhip.h");
+// source 0: the last solve's stage records, under the context lock on the MPC stream — the validity window of qmhip_policy_eval_feedback
+static int rollout_solve(qmhip_ctx* c, int R, const int32_t* inst, const double* t0, const double* x0, const double* t_end, const QmRolloutParams* prm, double* x_end, double* u_end, int32_t* mode_end,
+                         struct qmhip_rollout_summary* summary, qmhip_rollout_sample* trace, int32_t* count) { QM_GUARD(c);
+  QmRolloutSource src; src.solver = c->mpc.solver; src.in_flight = c->io.in_flight > 0 || c->tick.in_flight > 0; src.have_solution = c->have_solution; src.B = c->mpc.solved_B;
+  const char* msg = nullptr; const int adm = qm_rollout_admit(src, R, inst, t0, x0, t_end, prm, x_end, u_end, mode_end, trace, &msg);
+  if (adm != QM_RO_OK) { c->fail(std::string("qmhip_policy_rollout: ") + msg); return adm; }
+  hipSetDevice(c->device); const QmMpcBuffers& d = c->mpc.d;
+  QmPolicyArgs p; p.mb = d.mb; p.B = src.B; p.nmax = d.nmax; p.nev = d.nev; p.n_nodes = d.n_nodes; p.node_t = d.node_t; p.node_ev = d.node_ev; p.xs = d.xs; p.us = d.us; p.ev = d.ev; p.modes = d.modes;
+  c->rollout.enqueue(d.mb, d.st, p, d.stage, d.nmax, false, R, inst, t0, x0, t_end, *prm); c->rollout.wait();
+  const int rc = c->hipstate(); if (rc != QMHIP_OK) return rc;
+  c->rollout.hand_over(x_end, u_end, mode_end, summary, trace, count); return QMHIP_OK;
+}
+// source 1: the active publication, exactly the path of qmhip_policy_eval_published — the publication mutex, its stream, the slot's two events, *seq
+static int rollout_published(qmhip_ctx* c, int R, const int32_t* inst, const double* t0, const double* x0, const double* t_end, const QmRolloutParams* prm, double* x_end, double* u_end, int32_t* mode_end,
+                             struct qmhip_rollout_summary* summary, qmhip_rollout_sample* trace, int32_t* count, int64_t* seq) {
+  int rc = QMHIP_OK; std::string msg; const std::string fn = "qmhip_policy_rollout: ";
+  {
+    std::lock_guard<std::mutex> ev(c->eval_mu);
+    QmPubBook::Eval tk; QmRolloutSource src; src.published = c->pub.book.begin_eval(tk); src.gains = tk.gains; src.B = tk.B;
+    const char* why = nullptr; rc = qm_rollout_admit(src, R, inst, t0, x0, t_end, prm, x_end, u_end, mode_end, trace, &why);
+    if (rc != QM_RO_OK) { if (src.published) c->pub.book.end_eval(tk, false); msg = fn + why; }
+    else {
+      RolloutQueuePub& q = c->ro_qp; q.error.clear(); q.check(hipSetDevice(c->device), "hipSetDevice");
+      const QmPubSlot& s = c->pub.slot[tk.slot];
+      q.check(hipStreamWaitEvent(c->stream_p, (hipEvent_t)s.ev_pub, 0), "hipStreamWaitEvent");
+      const QmPolicyFbPubArgs pa = c->pub.eval_args(tk.slot, tk.B, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+      c->rollout_p.enqueue(c->mpc.d.mb, c->mpc.d.st, pa.p, s.gains, c->pub.W, true, R, inst, t0, x0, t_end, *prm);
+      q.check(hipEventRecord((hipEvent_t)s.ev_eval, c->stream_p), "hipEventRecord");
+      c->pub.book.end_eval(tk, true);      // enqueued: from here on a publication may go ahead (it is ordered behind this rollout by the slot's event)
+      c->rollout_p.wait();
+      if (!q.error.empty()) { rc = QMHIP_ERR_HIP; msg = fn + q.error; }
+      else { c->rollout_p.hand_over(x_end, u_end, mode_end, summary, trace, count); if (seq) *seq = (int64_t)tk.seq; }
+    }
+  }
+  if (rc != QMHIP_OK) { QM_GUARD(c); c->fail(msg); }      // (the context lock only for the error text, with nothing else held)
+  return rc;
+}
+int qmhip_policy_rollout(qmhip_ctx* c, int R, const int32_t* inst, const double* t0, const double* x0, const double* t_end, const qmhip_rollout_params* p, double* x_end, double* u_end, int32_t* mode_end,
+                         struct qmhip_rollout_summary* summary, qmhip_rollout_sample* trace, int32_t* count, int64_t* seq) {
+  if (!c) return QMHIP_ERR_ARG;
+  if (c->wbc_only) { QM_GUARD(c); c->fail("qmhip_policy_rollout: not available on a WBC-only context (qmhip_create_wbc_context)"); return QMHIP_ERR_STATE; }
+  QmRolloutParams copy; if (p) { copy.max_step = p->max_step; copy.max_steps = p->max_steps; copy.source = p->source; copy.feedback = p->feedback; copy.trace_cap = p->trace_cap; }
+  const QmRolloutParams* prm = p ? &copy : nullptr;
+  if (p && p->source == 1) return rollout_published(c, R, inst, t0, x0, t_end, prm, x_end, u_end, mode_end, summary, trace, count, seq);
+  return rollout_solve(c, R, inst, t0, x0, t_end, prm, x_end, u_end, mode_end, summary, trace, count);
 }
 
 // ---- streamed controller tick for a plant on the host (include/qmhip.h): measured rbd state in, hybrid joint command out ----

@@ -53,3 +53,12 @@ EPISODE_SUMMARY_FIELDS = [("t_first", "<f8", 1, 8 * EP_T_FIRST), ("t_last", "<f8
 _SI = 8 * ES_INTS
 EPISODE_SAMPLE_FIELDS = [("time", "<f8", 1, 8 * ES_TIME), ("rbd", "<f8", 55, 8 * ES_RBD), ("force_z", "<f8", 4, 8 * ES_FORCE_Z), ("tick", "<i4", 1, _SI), ("mode", "<i4", 1, _SI + 4),
                          ("contact_mask", "<i4", 1, _SI + 8), ("mpc_status", "<i4", 1, _SI + 12), ("qp_status", "<i4", 3, _SI + 16), ("sim_status", "<i4", 1, _SI + 28)]
+
+# struct qmhip_rollout_summary / qmhip_rollout_sample (include/qmhip_layout.h, the policy rollout), same form, from the QM_RS_* / QM_RT_* word offsets
+_RI = 8 * QM_RS_INTS
+ROLLOUT_SUMMARY_FIELDS = [("t_end", "<f8", 1, 8 * QM_RS_T_END), ("max_dev", "<f8", 4, 8 * QM_RS_MAX_DEV), ("max_fb", "<f8", 2, 8 * QM_RS_MAX_FB), ("min_cone", "<f8", 1, 8 * QM_RS_MIN_CONE),
+                          ("min_fz", "<f8", 1, 8 * QM_RS_MIN_FZ), ("max_swing_force", "<f8", 1, 8 * QM_RS_MAX_SWING), ("spare", "<f8", 2, 8 * QM_RS_SPARE),
+                          ("steps", "<i4", 1, _RI + 4 * QM_RS_I_STEPS), ("events", "<i4", 1, _RI + 4 * QM_RS_I_EVENTS), ("uncovered", "<i4", 1, _RI + 4 * QM_RS_I_UNCOVERED),
+                          ("flags", "<i4", 1, _RI + 4 * QM_RS_I_FLAGS), ("ispare", "<i4", 4, _RI + 4 * QM_RS_I_SPARE)]
+ROLLOUT_SAMPLE_FIELDS = [("t", "<f8", 1, 8 * QM_RT_TIME), ("x", "<f8", 30, 8 * QM_RT_X), ("u", "<f8", 30, 8 * QM_RT_U), ("mode", "<i4", 1, 8 * QM_RT_INTS), ("covered", "<i4", 1, 8 * QM_RT_INTS + 4),
+                         ("ispare", "<i4", 4, 8 * QM_RT_INTS + 8)]
