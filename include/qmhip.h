@@ -380,6 +380,25 @@ int qmhip_sim_step(qmhip_ctx* ctx, int B, double period, int n_substeps, double*
 int qmhip_sim_get_state(qmhip_ctx* ctx, int B, double* q, double* v, double* time, double* force /*[B][12]*/, int32_t* status /*[B]*/);
 /*      sim_get_rbd: rbd / contact of the plant's CURRENT state (what the last sim_step or sim_reset left) without stepping; either may be null */
 int qmhip_sim_get_rbd(qmhip_ctx* ctx, int B, double* rbd /*[B][55]*/, int32_t* contact /*[B][4]*/);
+/* ---- plant disturbances: scheduled external wrenches on the base and on the arm's end effector (a shove, a payload hanging from the gripper).  The reference has no
+ *      counterpart (Gazebo applies such wrenches through its own services); the semantics are this library's own.
+ *      sim_set_pushes: p is [B][K] records of struct qmhip_push, 96 bytes: qmhip_layout.h, with 0 <= K <= QM_SIM_MAX_PUSH; all vectors in the WORLD frame, times in ABSOLUTE plant time.  K == 0 or
+ *        p == NULL switches pushes off; sim_step and both closed loops then launch exactly the plant kernel they launch without the feature.  With a schedule they launch
+ *        its second instance, qm_sim_push_kernel (one wavefront per instance, the same LDS).  The schedule persists across qmhip_sim_reset and may be set before the first
+ *        one.  Instances at or beyond B of a later, larger step have no schedule.
+ *      ACTIVITY — slot k of instance b is active in a sub-step iff t_on <= t_s < t_off, t_s being the plant time at the START of that sub-step (the double the kernel
+ *        accumulates by repeated time += period / n_substeps).  t_on == t_off is never active; t_off = +inf is a permanent load; t_on = -inf is allowed.
+ *      APPLIED WRENCH — the sum over the active slots in ascending slot order, starting from +0.0; inactive slots are skipped, not multiplied by zero.
+ *      GENERALIZED FORCE — added to the right-hand side of M vdot = Sᵀ tau − nle + Σ J_iᵀ f_i before the solve, the velocity being [pdot_world, zyx rates, joint rates]:
+ *        base_force F acts at the base frame origin (q[0:3] = rbd[3:6]): rhs[0:3] += F;  base_torque n is a pure couple on the base body: rhs[3:6] += Eᵀ n with
+ *        omega_world = E(zyx) rates;  ee_force f acts at the arm's tip frame (frame 4, position rbd[48:51]): rhs += J_eeᵀ f with the linear 3 x 24 tip Jacobian, base
+ *        columns (identity, e_k x (p_tip − p_base)) included.
+ *      The hand-over launch of sim_reset (no sub-step) applies nothing.
+ *      Returns QMHIP_ERR_ARG with nothing changed for B outside [1, max_batch], K outside [0, QM_SIM_MAX_PUSH], a NaN time, a non-finite force / torque component.
+ *      sim_get_push: what the LAST sub-step of the last step applied — wrench[b] = {base_force, base_torque, ee_force} summed as above, mask[b] bit k set iff slot k was
+ *        active; either may be null.  Zeros after sim_reset and while pushes are off. */
+int qmhip_sim_set_pushes(qmhip_ctx* ctx, int B, int K, const qmhip_push* p /*[B][K]*/);
+int qmhip_sim_get_push(qmhip_ctx* ctx, int B, double* wrench /*[B][9]*/, int32_t* mask /*[B]*/);
 /*      closed_loop_sim: n_ticks of the whole controller around the plant, device resident — QMController::update + mpcThread_
  *        (qm_controllers/src/QMController.cpp:128-175, 202-244, 315-332): state estimate = the plant's state ("ground truth" estimator,
  *        currentObservation_.state = computeCentroidalStateFromRbdModel), an MPC call on that observation every mpc_every ticks (warm-started SQP; the

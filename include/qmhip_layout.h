@@ -239,6 +239,13 @@ typedef struct qmhip_plan_record {
 #define QM_FOOTHOLD_BYTES 40
 typedef struct qmhip_foothold { double time; int32_t leg, event; double pos[3]; } qmhip_foothold;
 
+/* one scheduled external wrench on the batched plant (qmhip.h, "plant disturbances"; qmhip_sim_set_pushes takes [B][K] of them, K <= QM_SIM_MAX_PUSH): active while
+   t_on <= t < t_off in absolute plant time; base_force [N] at the base frame origin, base_torque [Nm] a pure couple on the base body, ee_force [N] at the arm's tip
+   frame, all in the WORLD frame */
+#define QM_SIM_MAX_PUSH 8
+#define QM_PUSH_BYTES 96
+typedef struct qmhip_push { double t_on, t_off, base_force[3], base_torque[3], ee_force[3], spare; } qmhip_push;
+
 /* episode monitor (qmhip.h, "episode monitor"): per-instance running statistics of a device loop, folded behind every tick by the kernels of csrc/kernels/k_episode.h.
    EP_* are offsets in 8-byte WORDS of struct qmhip_episode_summary (32 words: 16 doubles, then 32 int32, two per word; EP_I_* are indices of those int32),
    ES_* offsets in 8-byte words of struct qmhip_episode_sample (64 words: 60 doubles, then 8 int32).  Feet in CONTACT order LF RF LH RH; a mask is 8 LF + 4 RF + 2 LH + RH */
@@ -357,6 +364,7 @@ static_assert(offsetof(qmhip_plan_record, mode) == 8 * PT_MODE && offsetof(qmhip
               offsetof(qmhip_plan_record, foot_force) == 8 * PT_FOOT_FORCE && offsetof(qmhip_plan_record, ee_pos) == 8 * PT_EE_POS && offsetof(qmhip_plan_record, ee_quat) == 8 * PT_EE_QUAT &&
               offsetof(qmhip_plan_record, ee_err) == 8 * PT_EE_ERR && offsetof(qmhip_plan_record, cop) == 8 * PT_COP && offsetof(qmhip_plan_record, spare) == 8 * PT_SPARE, "PT_* are the word offsets of qmhip_plan_record");
 static_assert(sizeof(qmhip_foothold) == QM_FOOTHOLD_BYTES && offsetof(qmhip_foothold, leg) == 8 && offsetof(qmhip_foothold, event) == 12 && offsetof(qmhip_foothold, pos) == 16, "qmhip_foothold is 40 bytes");
+static_assert(sizeof(qmhip_push) == QM_PUSH_BYTES && offsetof(qmhip_push, base_force) == 16 && offsetof(qmhip_push, base_torque) == 40 && offsetof(qmhip_push, ee_force) == 64 && offsetof(qmhip_push, spare) == 88, "qmhip_push is 12 doubles");
 #endif
 
 #endif

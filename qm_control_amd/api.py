@@ -29,7 +29,7 @@ EXPORTS = ["qmhip_create", "qmhip_create_from_blobs", "qmhip_create_wbc_context"
            "qmhip_step_submit", "qmhip_step_collect", "qmhip_step_in_flight",
            "qmhip_plan_task_space", "qmhip_plan_footholds", "qmhip_task_space_eval", "qmhip_policy_rollout",
            "qmhip_episode_monitor", "qmhip_episode_set_anchor", "qmhip_episode_summary", "qmhip_episode_trace", "qmhip_episode_fold",
-           "qmhip_tick_reset", "qmhip_tick_submit", "qmhip_tick_collect", "qmhip_observe", "qmhip_sim_get_rbd",
+           "qmhip_tick_reset", "qmhip_tick_submit", "qmhip_tick_collect", "qmhip_observe", "qmhip_sim_get_rbd", "qmhip_sim_set_pushes", "qmhip_sim_get_push",
            "qmhip_sim_set_params", "qmhip_sim_set_controller", "qmhip_sim_reset", "qmhip_sim_set_command", "qmhip_sim_step", "qmhip_sim_get_state", "qmhip_closed_loop_sim", "qmhip_closed_loop_sim_pipelined"]
 
 # struct qmhip_step_record (include/qmhip_layout.h) as a numpy structured dtype: one 1024-byte record per instance and control step
@@ -48,6 +48,9 @@ FOOTHOLD = _rec_dtype(L.FOOTHOLD_FIELDS, L.QM_FOOTHOLD_BYTES)
 # struct qmhip_episode_summary: one 256-byte record per instance of a monitored episode; struct qmhip_episode_sample: one 512-byte raw sample (QMHWSim.monitor)
 EPISODE_SUMMARY = _rec_dtype(L.EPISODE_SUMMARY_FIELDS, L.QM_EP_BYTES)
 EPISODE_SAMPLE = _rec_dtype(L.EPISODE_SAMPLE_FIELDS, L.QM_ES_BYTES)
+# struct qmhip_push: one scheduled external wrench on the plant, 96 bytes (QMHWSim.set_pushes)
+PUSH = _rec_dtype(L.PUSH_FIELDS, L.QM_PUSH_BYTES)
+SIM_MAX_PUSH = L.QM_SIM_MAX_PUSH
 # struct qmhip_rollout_summary: one 128-byte record per row of a policy rollout; qmhip_rollout_sample: one 512-byte trace sample per evaluation point (SqpMpc.rollout_policy)
 ROLLOUT_SUMMARY = _rec_dtype(L.ROLLOUT_SUMMARY_FIELDS, L.QM_RS_BYTES)
 ROLLOUT_SAMPLE = _rec_dtype(L.ROLLOUT_SAMPLE_FIELDS, L.QM_RT_BYTES)
@@ -517,6 +520,24 @@ class QMHWSim:
         B = self.B; rbd = np.zeros((B, 55)) if download else None; contact = np.zeros((B, 4), np.int32) if download else None
         self.itf._check(self.lib.qmhip_sim_step(self.itf.h, B, C.c_double(period), int(n_substeps), _p(rbd), _pi(contact)), "qmhip_sim_step")
         return rbd, contact
+
+    def set_pushes(self, p):
+        """schedule of external wrenches (qmhip_sim_set_pushes): p is [B][K] or [B] of dtype PUSH (K <= SIM_MAX_PUSH) — per slot a window t_on <= t < t_off of absolute
+        plant time (t_off = inf: a permanent load) and, in the world frame, base_force at the base origin, base_torque on the base body, ee_force at the arm's tip.
+        None switches pushes off.  The schedule persists across reset()"""
+        if p is None:
+            self.itf._check(self.lib.qmhip_sim_set_pushes(self.itf.h, 0, 0, None), "qmhip_sim_set_pushes"); return
+        p = np.ascontiguousarray(p, dtype=PUSH)
+        if p.ndim == 1:
+            p = p[:, None]
+        assert p.ndim == 2
+        self.itf._check(self.lib.qmhip_sim_set_pushes(self.itf.h, p.shape[0], p.shape[1], p.ctypes.data_as(C.c_void_p)), "qmhip_sim_set_pushes")
+
+    def push_state(self, B=None):
+        """(wrench [B][9], mask [B]): base force, base torque and end-effector force the last sub-step of the last step applied; bit k of mask: slot k was active"""
+        B = self.B if B is None else int(B); w = np.zeros((B, 9)); m = np.zeros(B, np.int32)
+        self.itf._check(self.lib.qmhip_sim_get_push(self.itf.h, B, _p(w), _pi(m)), "qmhip_sim_get_push")
+        return w, m
 
     def set_controller(self, kind):
         """0: qm::QMController, 1: qm::QMMpcController (HierarchicalMpcWbc + arm position commands at 100 Hz); call before reset()"""

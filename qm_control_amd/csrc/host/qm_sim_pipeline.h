@@ -14,7 +14,21 @@ struct QmSimBuffers {
   int p_nmax = 0, p_nev = 0; double* p_xs = nullptr; double* p_us = nullptr; double* p_node_t = nullptr; int* p_node_ev = nullptr; int* p_n_nodes = nullptr; double* p_ev = nullptr; int* p_modes = nullptr;
   bool p_valid = false;
   double* x_est = nullptr; double* t_est = nullptr;      // feedback policy: the tick's estimated centroidal state ([B][30]) on the ticks without an MPC call
+  // plant disturbances (qmhip_sim_set_pushes): the schedule [push_B][push_K] of struct qmhip_push (push_K = 0: none, the plain plant kernel runs), what the last
+  // sub-step applied ([Bmax][9]) and which slots were active ([Bmax])
+  double* push = nullptr; int push_K = 0, push_B = 0; double* push_out = nullptr; int* push_mask = nullptr;
 };
+
+// what qmhip_sim_set_pushes accepts: times may be infinite (a permanent load) but not NaN, every force / torque component is finite
+static_assert(sizeof(qmhip_push) == QM_PUSH_WORDS * 8, "the plant kernel reads struct qmhip_push as QM_PUSH_WORDS doubles");
+inline bool qm_pushes_valid(int B, int K, const double* p) {
+  for (size_t i = 0; i < (size_t)B * K; ++i) {
+    const double* r = p + i * QM_PUSH_WORDS;
+    if (r[0] != r[0] || r[1] != r[1]) return false;
+    for (int j = 2; j < 11; ++j) if (!(r[j] - r[j] == 0.0)) return false;      // inf - inf and NaN - NaN are NaN
+  }
+  return true;
+}
 
 template <class BK>
 struct QmSimPipeline {
@@ -28,14 +42,21 @@ struct QmSimPipeline {
     s.ring = A<double>((size_t)Bmax * QM_SIM_SLOTS * QM_SIM_CMD); s.ring_n = A<int>((size_t)Bmax * 2); s.rbd = A<double>((size_t)Bmax * QM_NRBD); s.contact = A<int>((size_t)Bmax * 4);
     s.force = A<double>((size_t)Bmax * 12); s.status = A<int>(Bmax);
     s.arm_hold = A<double>((size_t)Bmax * 6); s.arm_last = A<double>((size_t)Bmax * 6); s.x_est = A<double>((size_t)Bmax * 30); s.t_est = A<double>(Bmax);
+    s.push = A<double>((size_t)Bmax * QM_SIM_MAX_PUSH * QM_PUSH_WORDS); s.push_out = A<double>((size_t)Bmax * 9); s.push_mask = A<int>(Bmax);
   }
-  void release() { void* ps[] = {s.q, s.v, s.time, s.cmd, s.ring, s.ring_n, s.rbd, s.contact, s.force, s.status, s.arm_hold, s.arm_last, s.p_xs, s.p_us, s.p_node_t, s.p_node_ev, s.p_n_nodes, s.p_ev, s.p_modes, s.x_est, s.t_est}; for (void* ptr : ps) if (ptr) bk.free(ptr); s = QmSimBuffers(); }
+  void release() { void* ps[] = {s.q, s.v, s.time, s.cmd, s.ring, s.ring_n, s.rbd, s.contact, s.force, s.status, s.arm_hold, s.arm_last, s.p_xs, s.p_us, s.p_node_t, s.p_node_ev, s.p_n_nodes, s.p_ev, s.p_modes, s.x_est, s.t_est, s.push, s.push_out, s.push_mask}; for (void* ptr : ps) if (ptr) bk.free(ptr); s = QmSimBuffers(); }
   // "Simulation reset" of QMHWSim::writeSim: state set, delay buffer and held command cleared
   void reset(int B, const double* q_host, const double* v_host, const double* time_host) {
     s.p_valid = false;
     bk.to_device(s.q, q_host, (size_t)B * 24 * 8); bk.to_device(s.v, v_host, (size_t)B * 24 * 8); bk.to_device(s.time, time_host, (size_t)B * 8);
     bk.zero(s.ring_n, (size_t)s.Bmax * 2 * sizeof(int)); bk.zero(s.cmd, (size_t)s.Bmax * (QM_SIM_CMD - 1) * 8);
+    bk.zero(s.push_out, (size_t)s.Bmax * 9 * 8); bk.zero(s.push_mask, (size_t)s.Bmax * sizeof(int));      // nothing applied yet; the schedule itself (absolute plant time) stays
     QmArmResetArgs r; r.B = B; r.q = s.q; r.time = s.time; r.arm_hold = s.arm_hold; r.arm_last = s.arm_last; bk.launch(qm_arm_reset_kernel, (B * 6 + 63) / 64, 64, 0, r);
+  }
+  // schedule of external wrenches, [B][K] records of QM_PUSH_WORDS doubles (validated by the caller); K = 0 or a null pointer switches them off
+  void set_pushes(int B, int K, const double* host) {
+    if (K <= 0 || !host) { s.push_K = 0; s.push_B = 0; bk.zero(s.push_out, (size_t)s.Bmax * 9 * 8); bk.zero(s.push_mask, (size_t)s.Bmax * sizeof(int)); return; }
+    bk.to_device(s.push, host, (size_t)B * K * QM_PUSH_WORDS * 8); s.push_K = K; s.push_B = B;
   }
   void set_command(int B, const double* cmd_host) { bk.to_device(s.cmd, cmd_host, (size_t)B * (QM_SIM_CMD - 1) * 8); }
   // copy of the solver's primal solution + grid + mode schedule into the published-policy buffers
@@ -61,7 +82,10 @@ struct QmSimPipeline {
   void step(const double* mb_dev, int B, double period, int nsub) {
     QmSimArgs a; a.mb = mb_dev; a.B = B; a.nsub = nsub; a.h = nsub > 0 ? period / nsub : 0.0; a.p = p; a.q = s.q; a.v = s.v; a.time = s.time; a.cmd = s.cmd; a.ring = s.ring; a.ring_n = s.ring_n;
     a.rbd = s.rbd; a.contact = s.contact; a.force = s.force; a.status = s.status;
-    bk.launch(qm_sim_kernel, B, 64, SIM_LDS_BYTES, a);   // one wavefront per instance
+    if (s.push_K > 0) {                                  // a schedule is set: the instance of the kernel that applies it
+      QmSimPushArgs pa; pa.sim = a; pa.push.push = s.push; pa.push.K = s.push_K; pa.push.nB = s.push_B; pa.push.push_out = s.push_out; pa.push.push_mask = s.push_mask;
+      bk.launch(qm_sim_push_kernel, B, 64, SIM_LDS_BYTES, pa);
+    } else bk.launch(qm_sim_kernel, B, 64, SIM_LDS_BYTES, a);   // one wavefront per instance
   }
 };
 

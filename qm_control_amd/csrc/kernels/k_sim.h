@@ -15,6 +15,8 @@
 //   * QMHWSim::readSim (QMHWSim.cpp:60-75): joint / base state and the contact flags; the state is handed over in the estimator's
 //     rbd layout (qm_estimation/src/StateEstimateBase.cpp:41-103) so that the WBC and the MPC observation read it like the reference's
 //     "ground truth" estimator (FromTopiceEstimate).
+//   * external wrenches (no counterpart in the reference's sources): qm_sim_push_kernel, the second instance of the step's body, applies a schedule of base forces,
+//     base torques and end-effector forces (QmPushArgs); qm_sim_kernel is the instance without them.
 // Joint position limits and self collision are not modelled.
 #pragma once
 #include "qm_dev_rbd.h"
@@ -35,6 +37,15 @@ struct QmSimArgs {
   double* force;                        // [B][12] contact forces of the last sub-step (world frame)
   int* status;                          // [B] 0 ok, 1 mass matrix not positive definite
 };
+// scheduled external wrenches (struct qmhip_push, qmhip_layout.h; semantics: qmhip.h "plant disturbances"): slot k of instance b is active in a sub-step iff
+// t_on <= t_s < t_off with t_s the plant time at the START of the sub-step; the applied wrench is the sum over the active slots in ascending slot order from +0.0
+#define QM_PUSH_WORDS (QM_PUSH_BYTES / 8)   /* t_on, t_off, base_force(3), base_torque(3), ee_force(3), spare */
+struct QmPushArgs {
+  const double* push; int K; int nB;    // [nB][K][QM_PUSH_WORDS] schedule (world frame, absolute plant time); instances at or beyond nB have none
+  double* push_out;                     // [B][9] applied base force, base torque, end-effector force of the last sub-step
+  int* push_mask;                       // [B] bit k: slot k was active in the last sub-step
+};
+struct QmSimPushArgs { QmSimArgs sim; QmPushArgs push; };      // (one argument record per launch: the backends' launch() takes one)
 
 // ---- LDS carve (doubles) ----
 #define SL_M     0                      /* [24][24] */
@@ -47,15 +58,19 @@ struct QmSimArgs {
 #define SL_RHS   1092
 #define SL_F     1116                   /* [12] */
 #define SL_TAU   1128                   /* [18] */
-#define SL_JDUM  1146                   /* [6][24] sink of the arm Jacobian (not needed by the plant) */
+#define SL_JDUM  1146                   /* [6][24] sink of the arm Jacobian (not needed by the plant; its push instance keeps it: J_ee of an end-effector force) */
 #define SL_COMP  1290                   /* [19 x 6][6] per-joint subtree composites of the six chain lanes (lane interleaved; registers would spill) */
 #define SL_TOTAL (SL_COMP + 19 * 6 * 6)
 #define SIM_LDS_BYTES (SL_TOTAL * 8)
 
 // measured pass of one chain per lane (lanes 0-3 legs, 4 arm, 5 root body) + base block: M, nle, foot Jacobians, tips
+// PUSH: the arm lane keeps its tip Jacobian too — SL_JDUM is zeroed and then holds [lin(3); ang(3)][24], the linear rows with their base columns (the rows J_ee of an
+// end-effector force)
+template <bool PUSH>
 __device__ __forceinline__ void sim_dynamics_terms(const double* mb, double* S, const int l, const bool want_m) {
   double* M = S + SL_M; double* nle = S + SL_NLE; double* Jf = S + SL_JF; const double* q = S + SL_Q; const double* v = S + SL_V;
   for (int i = l; i < SL_TIP; i += 64) S[i] = 0.0;
+  if constexpr (PUSH) { if (want_m) for (int i = l; i < 6 * QM_NQ; i += 64) S[SL_JDUM + i] = 0.0; }
   qm_wave_sync();
   if (l < 6) {
     RbdBase Bb; rbd_base(q, v, Bb);
@@ -65,14 +80,16 @@ __device__ __forceinline__ void sim_dynamics_terms(const double* mb, double* S, 
       RbdJsink Jt; Jt.rows = leg ? Jf + 3 * contact * QM_NQ : S + SL_JDUM; Jt.nrows = leg ? 3 : 6; Jt.dummy = 0.0;
       RbdTip tip;
       RbdCompLds comp; comp.base = S + SL_COMP + l; comp.stride = 6;
-      rbd_chain<6, double*, RbdJsink, RbdCompLds>(mb, leg ? 3 * l : 12, contact, q, v, Bb, M, nle, want_m, cm, ch, cI, F, NO, (RbdSums*)nullptr, tip, Jt, want_m && leg, leg ? 3 : 6, comp);
-      if (leg) {
+      rbd_chain<6, double*, RbdJsink, RbdCompLds>(mb, leg ? 3 * l : 12, contact, q, v, Bb, M, nle, want_m, cm, ch, cI, F, NO, (RbdSums*)nullptr, tip, Jt, want_m && (PUSH || leg), leg ? 3 : 6, comp);
+      if (PUSH || leg) {
         if (want_m) {
           double* Jr = Jt.rows;
           for (int r = 0; r < 3; ++r) Jr[r * QM_NQ + r] = 1.0;
           for (int k = 0; k < 3; ++k) { const double e[3] = {Bb.E[k], Bb.E[3 + k], Bb.E[6 + k]}, d[3] = {tip.p[0] - Bb.p[0], tip.p[1] - Bb.p[1], tip.p[2] - Bb.p[2]}; double cr[3]; v3_cross(e, d, cr);
             for (int r = 0; r < 3; ++r) Jr[r * QM_NQ + 3 + k] = cr[r]; }
         }
+      }
+      if (leg) {
         for (int i = 0; i < 3; ++i) { S[SL_TIP + 6 * contact + i] = tip.p[i]; S[SL_TIP + 6 * contact + 3 + i] = tip.v[i]; }
       } else { for (int i = 0; i < 3; ++i) S[SL_TIP + 24 + i] = tip.p[i]; for (int i = 0; i < 9; ++i) S[SL_TIP + 27 + i] = tip.R[i]; }
     } else {
@@ -97,7 +114,8 @@ __device__ __forceinline__ void sim_dynamics_terms(const double* mb, double* S, 
   qm_wave_sync();
 }
 
-__global__ void __launch_bounds__(64) qm_sim_kernel(QmSimArgs a) {
+template <bool PUSH>
+__device__ __forceinline__ void sim_step_body(const QmSimArgs& a, const QmPushArgs& pa) {
   extern __shared__ double qm_smem[];
   double* S = qm_smem;
   const int b = blockIdx.x, l = threadIdx.x & 63;
@@ -109,6 +127,7 @@ __global__ void __launch_bounds__(64) qm_sim_kernel(QmSimArgs a) {
   int head = a.ring_n[b * 2], cnt = a.ring_n[b * 2 + 1];
   double* ring = a.ring + (size_t)b * QM_SIM_SLOTS * QM_SIM_CMD;
   int bad = 0;
+  double pw = 0.0; int pmask = 0;         // PUSH: lane l < 9 keeps component l of the applied wrench (base force, base torque, end-effector force); active slots
   qm_wave_sync();
   // ---- delay buffer (QMHWSim.cpp:100-110), once per call like writeSim once per simulation step: drop what is older than `delay`, push the held
   //      command with the current time stamp, apply the oldest survivor during this step ----
@@ -121,8 +140,15 @@ __global__ void __launch_bounds__(64) qm_sim_kernel(QmSimArgs a) {
   }
   const double* use = ring + ((head + (cnt > 0 ? cnt : 1) - 1) % QM_SIM_SLOTS) * QM_SIM_CMD;
   for (int s = 0; s < a.nsub; ++s) {
+    if constexpr (PUSH) {                 // the slots are tested at the time the sub-step STARTS at
+      pw = 0.0; pmask = 0;
+      if (b < pa.nB) for (int k = 0; k < pa.K; ++k) {
+        const double* P = pa.push + ((size_t)b * pa.K + k) * QM_PUSH_WORDS;
+        if (P[0] <= time && time < P[1]) { pmask |= 1 << k; if (l < 9) pw += P[2 + l]; }
+      }
+    }
     time += a.h;
-    sim_dynamics_terms(mb, S, l, true);
+    sim_dynamics_terms<PUSH>(mb, S, l, true);
     if (l >= 6 && l < 24) {
       const int j = l - 6;
       double t = use[1 + 36 + j] * (use[1 + j] - q[l]) + use[1 + 54 + j] * (use[1 + 18 + j] - v[l]) + use[1 + 72 + j];   // kp (posDes − q) + kd (velDes − qd) + ff
@@ -140,8 +166,17 @@ __global__ void __launch_bounds__(64) qm_sim_kernel(QmSimArgs a) {
       }
       fc[3 * l] = fx; fc[3 * l + 1] = fy; fc[3 * l + 2] = fz;
     }
+    if constexpr (PUSH) { if (l < 9) S[SL_ACC + l] = pw; }      // (the accumulators of sim_dynamics_terms are free between two of its calls)
     qm_wave_sync();
-    if (l < 24) { double r = ((l >= 6) ? tau[l - 6] : 0.0) - nle[l]; for (int k = 0; k < 12; ++k) r += Jf[k * QM_NQ + l] * fc[k]; rhs[l] = r; }
+    if (l < 24) { double r = ((l >= 6) ? tau[l - 6] : 0.0) - nle[l]; for (int k = 0; k < 12; ++k) r += Jf[k * QM_NQ + l] * fc[k];
+      if constexpr (PUSH) {               // generalized force of the wrench: F on the base translation, Eᵀ n on the zyx rates, J_eeᵀ f on every dof
+        const double* w = S + SL_ACC; const double* Je = S + SL_JDUM;
+        if (l < 3) r += w[l];
+        else if (l < 6) { double E[9]; euler_E<true>(q[3], q[4], E);
+          for (int k = 0; k < 3; ++k) if (l == 3 + k) r += E[k] * w[3] + E[3 + k] * w[4] + E[6 + k] * w[5]; }
+        for (int i = 0; i < 3; ++i) r += Je[i * QM_NQ + l] * w[6 + i];
+      }
+      rhs[l] = r; }
     qm_wave_sync();
     // ---- M = L Lᵀ in place (lower triangle), right-looking; lane i owns row i ----
     for (int k = 0; k < 24; ++k) {
@@ -165,7 +200,7 @@ __global__ void __launch_bounds__(64) qm_sim_kernel(QmSimArgs a) {
     qm_wave_sync();
   }
   // ---- hand-over: plant state, estimator-layout rbd state (FK of the arm tip at the final state), contact flags ----
-  sim_dynamics_terms(mb, S, l, false);
+  sim_dynamics_terms<PUSH>(mb, S, l, false);
   if (l < 24) { a.q[(size_t)b * 24 + l] = q[l]; a.v[(size_t)b * 24 + l] = v[l]; }
   double* r = a.rbd + (size_t)b * QM_NRBD;
   if (l < 3) { r[l] = q[3 + l]; r[3 + l] = q[l]; r[27 + l] = v[l]; }
@@ -175,4 +210,9 @@ __global__ void __launch_bounds__(64) qm_sim_kernel(QmSimArgs a) {
   if (l < 4) a.contact[b * 4 + l] = (a.p.foot_radius - S[SL_TIP + 6 * l + 2] > 0.0) ? 1 : 0;
   if (l < 12) a.force[(size_t)b * 12 + l] = (a.nsub > 0) ? fc[l] : 0.0;
   if (l == 0) { a.time[b] = time; a.ring_n[b * 2] = head; a.ring_n[b * 2 + 1] = cnt; a.status[b] = bad; }
+  if constexpr (PUSH) { if (l < 9) pa.push_out[(size_t)b * 9 + l] = pw; if (l == 0) pa.push_mask[b] = pmask; }      // nsub == 0 (hand-over): nothing applied
 }
+
+__global__ void __launch_bounds__(64) qm_sim_kernel(QmSimArgs a) { sim_step_body<false>(a, QmPushArgs()); }
+// the same step with the scheduled wrenches of QmPushArgs applied (one wavefront per instance, the same LDS carve)
+__global__ void __launch_bounds__(64) qm_sim_push_kernel(QmSimPushArgs a) { sim_step_body<true>(a.sim, a.push); }

@@ -36,6 +36,8 @@ PLAN_RECORD_FIELDS = [("time", "<f8", 1, 8 * PT_TIME), ("mode", "<i4", 1, 8 * PT
                       ("foot_pos", "<f8", (4, 3), 8 * PT_FOOT_POS), ("foot_vel", "<f8", (4, 3), 8 * PT_FOOT_VEL), ("foot_force", "<f8", (4, 3), 8 * PT_FOOT_FORCE),
                       ("ee_pos", "<f8", 3, 8 * PT_EE_POS), ("ee_quat", "<f8", 4, 8 * PT_EE_QUAT), ("ee_err", "<f8", 6, 8 * PT_EE_ERR), ("cop", "<f8", 3, 8 * PT_COP), ("spare", "<f8", 4, 8 * PT_SPARE)]
 FOOTHOLD_FIELDS = [("time", "<f8", 1, 0), ("leg", "<i4", 1, 8), ("event", "<i4", 1, 12), ("pos", "<f8", 3, 16)]
+# struct qmhip_push (include/qmhip_layout.h): one scheduled external wrench on the plant
+PUSH_FIELDS = [("t_on", "<f8", 1, 0), ("t_off", "<f8", 1, 8), ("base_force", "<f8", 3, 16), ("base_torque", "<f8", 3, 40), ("ee_force", "<f8", 3, 64), ("spare", "<f8", 1, 88)]
 
 # struct qmhip_episode_summary / qmhip_episode_sample (include/qmhip_layout.h, the episode monitor), same form, from the EP_* / ES_* word offsets
 _EI = 8 * EP_INTS
