@@ -399,6 +399,34 @@ int qmhip_sim_get_rbd(qmhip_ctx* ctx, int B, double* rbd /*[B][55]*/, int32_t* c
  *        active; either may be null.  Zeros after sim_reset and while pushes are off. */
 int qmhip_sim_set_pushes(qmhip_ctx* ctx, int B, int K, const qmhip_push* p /*[B][K]*/);
 int qmhip_sim_get_push(qmhip_ctx* ctx, int B, double* wrench /*[B][9]*/, int32_t* mask /*[B]*/);
+/* ---- sensor model: white noise, a constant bias and a latency of whole samples, per instance, on what the CONTROLLER is told about the plant.  The reference's simulation
+ *      has only the "ground truth" estimator (FromTopiceEstimate); the semantics are this library's own.  The plant, qmhip_sim_step / qmhip_sim_get_rbd / _get_state and the
+ *      episode monitor (fall check included) keep the truth; the MPC observation, the tick's state estimate, the WBC and updateControlLaw of both closed loops read the
+ *      measured state.  Contact flags are not modelled (the loops use the planned mode), `time` stays the plant's time; no quantisation, no coloured noise.
+ *      sim_set_sensors: s is [B] records of struct qmhip_sensor, 128 bytes: qmhip_layout.h; s == NULL switches the model off — every entry point then launches exactly what it
+ *        launches without the feature.  With records, every plant launch is followed by one qm_sense_kernel (one wavefront per instance).  May be called before the first
+ *        sim_reset; the records persist across sim_reset.  Instances at or beyond B of a larger step have no record: their measured state is a copy of the truth.
+ *      GROUPS g of the 55-entry rbd state (qm_estimation/src/StateEstimateBase.cpp:41-103): 0 rbd[0:3] base zyx angles, 1 rbd[3:6] base position, 2 rbd[6:24] joint positions,
+ *        3 rbd[24:27] base angular velocity, 4 rbd[27:30] base linear velocity, 5 rbd[30:48] joint rates.  Component index c = 0..47 is the rbd index.
+ *      SAMPLES — the hand-over launch of sim_reset takes sample n = 0; every plant step (sim_step, a tick of either loop) takes sample n + 1.  A per-instance ring keeps the
+ *        true rbd state of the last QM_SENSE_MAX_LAG + 1 samples, sample n in slot n % (QM_SENSE_MAX_LAG + 1).  The SOURCE of sample n is the truth x of sample
+ *        n − min(lag, n): before `lag` samples exist, the oldest one (the reset state).
+ *      NOISE — integer arithmetic mod 2^64: mix(z): z = (z ^ z>>30) * 0xBF58476D1CE4E5B9; z = (z ^ z>>27) * 0x94D049BB133111EB; return z ^ z>>31.
+ *        word(seed, n, c, w) = mix(mix(seed + G (n + 1)) + G (2c + w + 1)) with G = 0x9E3779B97F4A7C15 and n as a 64-bit unsigned value.  s = the sum of the eight 16-bit
+ *        fields of word(seed, n, c, 0) and word(seed, n, c, 1).  nu(seed, n, c) = (double)(2s − 8·65535) · C with C = 0x1.3988e1412ed76p-17, the double nearest
+ *        1 / sqrt(8 (65536² − 1) / 3): an eight-term Irwin-Hall variable of unit variance, |nu| <= 8·65535·C ≈ 4.8989.  The bias draw of component c is
+ *        nu_bias = nu(seed, 2^64 − 1, c) (the inner term of word is then seed + 0): a function of the seed alone, constant over the episode, stored nowhere.
+ *      MEASURED VALUE of component c in group g:  m = (x + bias_sigma[g] nu_bias) + sigma[g] nu(seed, n, c) — two products, the inner sum, the outer sum, each rounded on
+ *        its own (no fused multiply-add).  A group with sigma[g] == 0 and bias_sigma[g] == 0 is COPIED, not added to.
+ *      END-EFFECTOR POSE rbd[48:55] — an instance without a noisy group: all 55 entries are the source sample's, delayed truth bit for bit (lag 0: the truth itself, the
+ *        instance behaves as with the model off).  Otherwise: forward kinematics of the MEASURED configuration (StateEstimateBase::updateArmEE, StateEstimateBase.cpp:80-103).
+ *      Calling sim_set_sensors starts the sample count over: if the plant has been reset, sample 0 is taken from its current state at once (one qm_sense_kernel launch, no
+ *        plant launch).  Returns QMHIP_ERR_ARG with nothing changed for B outside [1, max_batch], a lag outside [0, QM_SENSE_MAX_LAG], a negative or non-finite sigma /
+ *        bias_sigma; QMHIP_ERR_STATE on a WBC-only context.
+ *      sim_get_measured: what the loops consume — with the model off the truth and samples[b] = 0, with it on the measured state and the index n of the last sample; either may
+ *        be null.  Errors as qmhip_sim_get_rbd. */
+int qmhip_sim_set_sensors(qmhip_ctx* ctx, int B, const qmhip_sensor* s /*[B], NULL: off*/);
+int qmhip_sim_get_measured(qmhip_ctx* ctx, int B, double* rbd /*[B][55]*/, int32_t* samples /*[B]*/);
 /*      closed_loop_sim: n_ticks of the whole controller around the plant, device resident — QMController::update + mpcThread_
  *        (qm_controllers/src/QMController.cpp:128-175, 202-244, 315-332): state estimate = the plant's state ("ground truth" estimator,
  *        currentObservation_.state = computeCentroidalStateFromRbdModel), an MPC call on that observation every mpc_every ticks (warm-started SQP; the

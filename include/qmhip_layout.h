@@ -246,6 +246,15 @@ typedef struct qmhip_foothold { double time; int32_t leg, event; double pos[3]; 
 #define QM_PUSH_BYTES 96
 typedef struct qmhip_push { double t_on, t_off, base_force[3], base_torque[3], ee_force[3], spare; } qmhip_push;
 
+/* sensor model of one instance of the batched plant (qmhip.h, "sensor model"; qmhip_sim_set_sensors takes [B] of them): what the controller is told is the plant's rbd
+   state of `lag` samples ago plus, per group g of the rbd state (0 base zyx angles rbd[0:3], 1 base position [3:6], 2 joint positions [6:24], 3 base angular velocity
+   [24:27], 4 base linear velocity [27:30], 5 joint rates [30:48]), a constant bias of standard deviation bias_sigma[g] and white noise of standard deviation sigma[g],
+   both drawn from `seed` by integer arithmetic */
+#define QM_SENSE_GROUPS 6
+#define QM_SENSE_MAX_LAG 8
+#define QM_SENSE_BYTES 128
+typedef struct qmhip_sensor { uint64_t seed; int32_t lag; int32_t spare0; double sigma[6]; double bias_sigma[6]; double spare[2]; } qmhip_sensor;
+
 /* episode monitor (qmhip.h, "episode monitor"): per-instance running statistics of a device loop, folded behind every tick by the kernels of csrc/kernels/k_episode.h.
    EP_* are offsets in 8-byte WORDS of struct qmhip_episode_summary (32 words: 16 doubles, then 32 int32, two per word; EP_I_* are indices of those int32),
    ES_* offsets in 8-byte words of struct qmhip_episode_sample (64 words: 60 doubles, then 8 int32).  Feet in CONTACT order LF RF LH RH; a mask is 8 LF + 4 RF + 2 LH + RH */
@@ -365,6 +374,8 @@ static_assert(offsetof(qmhip_plan_record, mode) == 8 * PT_MODE && offsetof(qmhip
               offsetof(qmhip_plan_record, ee_err) == 8 * PT_EE_ERR && offsetof(qmhip_plan_record, cop) == 8 * PT_COP && offsetof(qmhip_plan_record, spare) == 8 * PT_SPARE, "PT_* are the word offsets of qmhip_plan_record");
 static_assert(sizeof(qmhip_foothold) == QM_FOOTHOLD_BYTES && offsetof(qmhip_foothold, leg) == 8 && offsetof(qmhip_foothold, event) == 12 && offsetof(qmhip_foothold, pos) == 16, "qmhip_foothold is 40 bytes");
 static_assert(sizeof(qmhip_push) == QM_PUSH_BYTES && offsetof(qmhip_push, base_force) == 16 && offsetof(qmhip_push, base_torque) == 40 && offsetof(qmhip_push, ee_force) == 64 && offsetof(qmhip_push, spare) == 88, "qmhip_push is 12 doubles");
+static_assert(sizeof(qmhip_sensor) == QM_SENSE_BYTES && offsetof(qmhip_sensor, seed) == 0 && offsetof(qmhip_sensor, lag) == 8 && offsetof(qmhip_sensor, spare0) == 12 && offsetof(qmhip_sensor, sigma) == 16 &&
+              offsetof(qmhip_sensor, bias_sigma) == 16 + 8 * QM_SENSE_GROUPS && offsetof(qmhip_sensor, spare) == 16 + 16 * QM_SENSE_GROUPS, "qmhip_sensor is 16 eight-byte words");
 #endif
 
 #endif

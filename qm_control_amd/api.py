@@ -29,7 +29,7 @@ EXPORTS = ["qmhip_create", "qmhip_create_from_blobs", "qmhip_create_wbc_context"
            "qmhip_step_submit", "qmhip_step_collect", "qmhip_step_in_flight",
            "qmhip_plan_task_space", "qmhip_plan_footholds", "qmhip_task_space_eval", "qmhip_policy_rollout",
            "qmhip_episode_monitor", "qmhip_episode_set_anchor", "qmhip_episode_summary", "qmhip_episode_trace", "qmhip_episode_fold",
-           "qmhip_tick_reset", "qmhip_tick_submit", "qmhip_tick_collect", "qmhip_observe", "qmhip_sim_get_rbd", "qmhip_sim_set_pushes", "qmhip_sim_get_push",
+           "qmhip_tick_reset", "qmhip_tick_submit", "qmhip_tick_collect", "qmhip_observe", "qmhip_sim_get_rbd", "qmhip_sim_set_pushes", "qmhip_sim_get_push", "qmhip_sim_set_sensors", "qmhip_sim_get_measured",
            "qmhip_sim_set_params", "qmhip_sim_set_controller", "qmhip_sim_reset", "qmhip_sim_set_command", "qmhip_sim_step", "qmhip_sim_get_state", "qmhip_closed_loop_sim", "qmhip_closed_loop_sim_pipelined"]
 
 # struct qmhip_step_record (include/qmhip_layout.h) as a numpy structured dtype: one 1024-byte record per instance and control step
@@ -51,6 +51,9 @@ EPISODE_SAMPLE = _rec_dtype(L.EPISODE_SAMPLE_FIELDS, L.QM_ES_BYTES)
 # struct qmhip_push: one scheduled external wrench on the plant, 96 bytes (QMHWSim.set_pushes)
 PUSH = _rec_dtype(L.PUSH_FIELDS, L.QM_PUSH_BYTES)
 SIM_MAX_PUSH = L.QM_SIM_MAX_PUSH
+# struct qmhip_sensor: the sensor model of one instance of the plant, 128 bytes (QMHWSim.set_sensors)
+SENSOR = _rec_dtype(L.SENSOR_FIELDS, L.QM_SENSE_BYTES)
+SENSE_MAX_LAG, SENSE_GROUPS = L.QM_SENSE_MAX_LAG, L.QM_SENSE_GROUPS
 # struct qmhip_rollout_summary: one 128-byte record per row of a policy rollout; qmhip_rollout_sample: one 512-byte trace sample per evaluation point (SqpMpc.rollout_policy)
 ROLLOUT_SUMMARY = _rec_dtype(L.ROLLOUT_SUMMARY_FIELDS, L.QM_RS_BYTES)
 ROLLOUT_SAMPLE = _rec_dtype(L.ROLLOUT_SAMPLE_FIELDS, L.QM_RT_BYTES)
@@ -538,6 +541,23 @@ class QMHWSim:
         B = self.B if B is None else int(B); w = np.zeros((B, 9)); m = np.zeros(B, np.int32)
         self.itf._check(self.lib.qmhip_sim_get_push(self.itf.h, B, _p(w), _pi(m)), "qmhip_sim_get_push")
         return w, m
+
+    def set_sensors(self, s):
+        """sensor model between the plant and the controller (qmhip_sim_set_sensors): s is [B] of dtype SENSOR — per instance a seed, a latency `lag` of whole samples
+        (<= SENSE_MAX_LAG) and, per group of the rbd state (base zyx, base position, joint positions, base angular velocity, base linear velocity, joint rates), the standard
+        deviations sigma of white noise and bias_sigma of a constant bias.  None switches the model off.  closed_loop() then controls on the measured state; step(), rbd(),
+        state() and the episode monitor keep the truth.  The records persist across reset(); the sample count starts over"""
+        if s is None:
+            self.itf._check(self.lib.qmhip_sim_set_sensors(self.itf.h, 0, None), "qmhip_sim_set_sensors"); return
+        s = np.ascontiguousarray(s, dtype=SENSOR)
+        assert s.ndim == 1
+        self.itf._check(self.lib.qmhip_sim_set_sensors(self.itf.h, s.shape[0], s.ctypes.data_as(C.c_void_p)), "qmhip_sim_set_sensors")
+
+    def measured(self, B=None):
+        """(rbd [B][55], samples [B]): the state the loops consume and the index of the last sample — the truth and zeros while the sensor model is off"""
+        B = self.B if B is None else int(B); rbd = np.zeros((B, 55)); n = np.zeros(B, np.int32)
+        self.itf._check(self.lib.qmhip_sim_get_measured(self.itf.h, B, _p(rbd), _pi(n)), "qmhip_sim_get_measured")
+        return rbd, n
 
     def set_controller(self, kind):
         """0: qm::QMController, 1: qm::QMMpcController (HierarchicalMpcWbc + arm position commands at 100 Hz); call before reset()"""

@@ -3,6 +3,7 @@
 #include "qm_pipeline.h"
 #include "qm_wbc_pipeline.h"
 #include "../kernels/k_sim.h"
+#include "../kernels/k_sense.h"
 #include "../kernels/k_loop.h"
 
 struct QmSimBuffers {
@@ -17,6 +18,9 @@ struct QmSimBuffers {
   // plant disturbances (qmhip_sim_set_pushes): the schedule [push_B][push_K] of struct qmhip_push (push_K = 0: none, the plain plant kernel runs), what the last
   // sub-step applied ([Bmax][9]) and which slots were active ([Bmax])
   double* push = nullptr; int push_K = 0, push_B = 0; double* push_out = nullptr; int* push_mask = nullptr;
+  // sensor model (qmhip_sim_set_sensors): the records [sense_B] of struct qmhip_sensor (sense_on false: off, nothing of k_sense.h is launched and the controller reads rbd),
+  // the truth of the last samples [Bmax][QM_SENSE_SLOTS][55], the index of the last sample [Bmax], what the controller is told [Bmax][55]; plant_B: batch of the last reset
+  unsigned long long* sense = nullptr; bool sense_on = false; int sense_B = 0; double* sense_ring = nullptr; int* sense_n = nullptr; double* rbd_meas = nullptr; int plant_B = 0;
 };
 
 // what qmhip_sim_set_pushes accepts: times may be infinite (a permanent load) but not NaN, every force / torque component is finite
@@ -26,6 +30,16 @@ inline bool qm_pushes_valid(int B, int K, const double* p) {
     const double* r = p + i * QM_PUSH_WORDS;
     if (r[0] != r[0] || r[1] != r[1]) return false;
     for (int j = 2; j < 11; ++j) if (!(r[j] - r[j] == 0.0)) return false;      // inf - inf and NaN - NaN are NaN
+  }
+  return true;
+}
+
+// what qmhip_sim_set_sensors accepts: a lag of 0 .. QM_SENSE_MAX_LAG samples, standard deviations that are finite and not negative
+static_assert(sizeof(qmhip_sensor) == QM_SENSE_WORDS * 8, "the sensor kernel reads struct qmhip_sensor as QM_SENSE_WORDS 8-byte words");
+inline bool qm_sensors_valid(int B, const qmhip_sensor* r) {
+  for (int b = 0; b < B; ++b) {
+    if (r[b].lag < 0 || r[b].lag > QM_SENSE_MAX_LAG) return false;
+    for (int g = 0; g < QM_SENSE_GROUPS; ++g) if (!(r[b].sigma[g] >= 0.0 && r[b].sigma[g] - r[b].sigma[g] == 0.0 && r[b].bias_sigma[g] >= 0.0 && r[b].bias_sigma[g] - r[b].bias_sigma[g] == 0.0)) return false;
   }
   return true;
 }
@@ -43,11 +57,12 @@ struct QmSimPipeline {
     s.force = A<double>((size_t)Bmax * 12); s.status = A<int>(Bmax);
     s.arm_hold = A<double>((size_t)Bmax * 6); s.arm_last = A<double>((size_t)Bmax * 6); s.x_est = A<double>((size_t)Bmax * 30); s.t_est = A<double>(Bmax);
     s.push = A<double>((size_t)Bmax * QM_SIM_MAX_PUSH * QM_PUSH_WORDS); s.push_out = A<double>((size_t)Bmax * 9); s.push_mask = A<int>(Bmax);
+    s.sense = A<unsigned long long>((size_t)Bmax * QM_SENSE_WORDS); s.sense_ring = A<double>((size_t)Bmax * QM_SENSE_SLOTS * QM_NRBD); s.sense_n = A<int>(Bmax); s.rbd_meas = A<double>((size_t)Bmax * QM_NRBD);
   }
-  void release() { void* ps[] = {s.q, s.v, s.time, s.cmd, s.ring, s.ring_n, s.rbd, s.contact, s.force, s.status, s.arm_hold, s.arm_last, s.p_xs, s.p_us, s.p_node_t, s.p_node_ev, s.p_n_nodes, s.p_ev, s.p_modes, s.x_est, s.t_est, s.push, s.push_out, s.push_mask}; for (void* ptr : ps) if (ptr) bk.free(ptr); s = QmSimBuffers(); }
+  void release() { void* ps[] = {s.q, s.v, s.time, s.cmd, s.ring, s.ring_n, s.rbd, s.contact, s.force, s.status, s.arm_hold, s.arm_last, s.p_xs, s.p_us, s.p_node_t, s.p_node_ev, s.p_n_nodes, s.p_ev, s.p_modes, s.x_est, s.t_est, s.push, s.push_out, s.push_mask, s.sense, s.sense_ring, s.sense_n, s.rbd_meas}; for (void* ptr : ps) if (ptr) bk.free(ptr); s = QmSimBuffers(); }
   // "Simulation reset" of QMHWSim::writeSim: state set, delay buffer and held command cleared
   void reset(int B, const double* q_host, const double* v_host, const double* time_host) {
-    s.p_valid = false;
+    s.p_valid = false; s.plant_B = B;
     bk.to_device(s.q, q_host, (size_t)B * 24 * 8); bk.to_device(s.v, v_host, (size_t)B * 24 * 8); bk.to_device(s.time, time_host, (size_t)B * 8);
     bk.zero(s.ring_n, (size_t)s.Bmax * 2 * sizeof(int)); bk.zero(s.cmd, (size_t)s.Bmax * (QM_SIM_CMD - 1) * 8);
     bk.zero(s.push_out, (size_t)s.Bmax * 9 * 8); bk.zero(s.push_mask, (size_t)s.Bmax * sizeof(int));      // nothing applied yet; the schedule itself (absolute plant time) stays
@@ -57,6 +72,19 @@ struct QmSimPipeline {
   void set_pushes(int B, int K, const double* host) {
     if (K <= 0 || !host) { s.push_K = 0; s.push_B = 0; bk.zero(s.push_out, (size_t)s.Bmax * 9 * 8); bk.zero(s.push_mask, (size_t)s.Bmax * sizeof(int)); return; }
     bk.to_device(s.push, host, (size_t)B * K * QM_PUSH_WORDS * 8); s.push_K = K; s.push_B = B;
+  }
+  // sensor records [B] (validated by the caller), a null pointer switches the model off.  The sample count starts over: a plant that has been reset hands sample 0 over
+  // from its current state at once (one launch of the sensor kernel, none of the plant)
+  void set_sensors(const double* mb_dev, int B, const qmhip_sensor* host) {
+    if (!host) { s.sense_on = false; s.sense_B = 0; bk.zero(s.sense_n, (size_t)s.Bmax * sizeof(int)); return; }
+    bk.to_device(s.sense, host, (size_t)B * QM_SENSE_BYTES); s.sense_on = true; s.sense_B = B;
+    if (s.plant_B > 0) sense(mb_dev, s.plant_B, true);
+  }
+  // the state the controller is given: the sensor model's output, or the plant's state itself
+  const double* meas_rbd() const { return s.sense_on ? s.rbd_meas : s.rbd; }
+  void sense(const double* mb_dev, int B, bool restart) {
+    QmSenseArgs g; g.mb = mb_dev; g.B = B; g.nB = s.sense_B; g.restart = restart ? 1 : 0; g.rec = s.sense; g.rbd = s.rbd; g.ring = s.sense_ring; g.n = s.sense_n; g.meas = s.rbd_meas;
+    bk.launch(qm_sense_kernel, B, 64, SENSE_LDS_BYTES, g);      // one wavefront per instance
   }
   void set_command(int B, const double* cmd_host) { bk.to_device(s.cmd, cmd_host, (size_t)B * (QM_SIM_CMD - 1) * 8); }
   // copy of the solver's primal solution + grid + mode schedule into the published-policy buffers
@@ -69,13 +97,13 @@ struct QmSimPipeline {
     s.p_valid = true;
   }
   // currentObservation_ of the MPC (x0, t0) from the plant state
-  void observe(const QmMpcBuffers& d, int B) { QmObserveArgs o; o.mb = d.mb; o.B = B; o.rbd = s.rbd; o.time = s.time; o.x0 = d.x0; o.t0 = d.t0; bk.launch(qm_observe_kernel, (B + 63) / 64, 64, 0, o); }
+  void observe(const QmMpcBuffers& d, int B) { QmObserveArgs o; o.mb = d.mb; o.B = B; o.rbd = meas_rbd(); o.time = s.time; o.x0 = d.x0; o.t0 = d.t0; bk.launch(qm_observe_kernel, (B + 63) / 64, 64, 0, o); }
   // the same estimate on a tick between two MPC calls (feedback policy): the observation stays out of the solver's x0 / t0
-  void estimate(const QmMpcBuffers& d, int B) { QmObserveArgs o; o.mb = d.mb; o.B = B; o.rbd = s.rbd; o.time = s.time; o.x0 = s.x_est; o.t0 = s.t_est; bk.launch(qm_observe_kernel, (B + 63) / 64, 64, 0, o); }
+  void estimate(const QmMpcBuffers& d, int B) { QmObserveArgs o; o.mb = d.mb; o.B = B; o.rbd = meas_rbd(); o.time = s.time; o.x0 = s.x_est; o.t0 = s.t_est; bk.launch(qm_observe_kernel, (B + 63) / 64, 64, 0, o); }
   // hybrid joint command from the evaluated policy and the WBC torques
   void command(int B, const double* x_des, const double* u_des, const double* wbc_out, double arm_kp, double arm_kd) {
     QmCommandArgs c; c.B = B; c.x_des = x_des; c.u_des = u_des; c.wbc_out = wbc_out; c.time = s.time; c.arm_kp = arm_kp; c.arm_kd = arm_kd; c.cmd = s.cmd;
-    c.controller = controller; c.rbd = s.rbd; c.arm_hold = s.arm_hold; c.arm_last = s.arm_last;
+    c.controller = controller; c.rbd = meas_rbd(); c.arm_hold = s.arm_hold; c.arm_last = s.arm_last;
     bk.launch(qm_command_kernel, (B * QM_NJ + 63) / 64, 64, 0, c);
   }
   // rbd state / contact flags of the current plant state without advancing it (nsub = 0 is not a step: the delay buffer is left alone)
@@ -86,6 +114,7 @@ struct QmSimPipeline {
       QmSimPushArgs pa; pa.sim = a; pa.push.push = s.push; pa.push.K = s.push_K; pa.push.nB = s.push_B; pa.push.push_out = s.push_out; pa.push.push_mask = s.push_mask;
       bk.launch(qm_sim_push_kernel, B, 64, SIM_LDS_BYTES, pa);
     } else bk.launch(qm_sim_kernel, B, 64, SIM_LDS_BYTES, a);   // one wavefront per instance
+    if (s.sense_on) sense(mb_dev, B, nsub == 0);         // sensors are on: one sample behind the step; the hand-over of a reset is sample 0
   }
 };
 
@@ -115,7 +144,7 @@ void qm_closed_loop_sim_ticks(BK& bk, QmMpcPipeline<BK>& mpc, QmWbcPipeline<BK>&
     // first tick after a reset: inputLast_ primed with the planned input (the reference's WBC has been running since time 0 when the legs are switched on at
     // time 10): zero joint acceleration
     if (sim_ticks == 0) bk.copy_dd(wbc.w.input_last, wbc.w.u_des, (size_t)B * 30 * 8);
-    wbc.step(mpc.d, B, period, sim.controller == 1 ? 1 : 0, sim.s.rbd, sim.s.time);      // QMMpcController::setupWbc installs HierarchicalMpcWbc (QMController.cpp:410-414)
+    wbc.step(mpc.d, B, period, sim.controller == 1 ? 1 : 0, sim.meas_rbd(), sim.s.time);      // QMMpcController::setupWbc installs HierarchicalMpcWbc (QMController.cpp:410-414)
     sim.command(B, wbc.w.x_des, wbc.w.u_des, wbc.w.out, arm_kp, arm_kd);
     sim.step(mpc.d.mb, B, period, n_substeps);
     if constexpr (Epi::enabled) { if (epi && epi->on) epi->tick_fold(mpc.d.mb, B, sim_ticks, period, sim.s, wbc.w); }
@@ -152,7 +181,7 @@ void qm_closed_loop_sim_pipelined(BK& bk, QmMpcPipeline<BK>& mpc, QmWbcPipeline<
     for (int k = 0; k < mpc_every; ++k) {
       policy();
       if (sim_ticks == 0) bk.copy_dd(wbc.w.input_last, wbc.w.u_des, (size_t)B * 30 * 8);
-      wbc.step(mpc.d, B, period, sim.controller == 1 ? 1 : 0, sim.s.rbd, sim.s.time);
+      wbc.step(mpc.d, B, period, sim.controller == 1 ? 1 : 0, sim.meas_rbd(), sim.s.time);
       sim.command(B, wbc.w.x_des, wbc.w.u_des, wbc.w.out, arm_kp, arm_kd);
       sim.step(mpc.d.mb, B, period, n_substeps);
       if constexpr (Epi::enabled) { if (epi && epi->on) epi->tick_fold(mpc.d.mb, B, sim_ticks, period, sim.s, wbc.w); }

@@ -53,7 +53,7 @@ struct HipBackend {
     const void* p = (const void*)k;
     if (p == (const void*)qm_grid_kernel || p == (const void*)qm_grid_nodes_kernel || p == (const void*)qm_save_grid_kernel || p == (const void*)qm_advance_kernel) return "grid"; if (p == (const void*)qm_lq_kernel || p == (const void*)qm_lq_dbg_kernel || p == (const void*)qm_lq_ipm_kernel) return "lq"; if (p == (const void*)qm_lq_m18_kernel) return "lq_m18"; if (p == (const void*)qm_lq_kin_kernel) return "lq_kin"; if (p == (const void*)qm_riccati_kernel || p == (const void*)qm_riccati_prof_kernel) return "riccati";
     if (p == (const void*)qm_ls_eval_kernel || p == (const void*)qm_ls_eval_dense_kernel || p == (const void*)qm_ls_eval_ipm_kernel) return "ls_eval";
-    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel || p == (const void*)(QmPolicyRolloutFn)qm_policy_rollout_kernel<QmFbStageView, SR_SIZE, false> || p == (const void*)(QmPolicyRolloutFn)qm_policy_rollout_kernel<QmFbPubView, PR_SIZE, true>) return "rollout"; if (p == (const void*)qm_sim_kernel || p == (const void*)qm_sim_push_kernel) return "sim"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_policy_fb_kernel || p == (const void*)qm_policy_fb_pub_kernel) return "policy_fb"; if (p == (const void*)qm_policy_publish_kernel) return "publish"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io"; if (p == (const void*)qm_tick_state_kernel || p == (const void*)qm_tick_pack_kernel) return "tick"; if (p == (const void*)qm_plan_nodes_kernel) return "plan_nodes"; if (p == (const void*)qm_plan_states_kernel) return "plan_states"; if (p == (const void*)qm_plan_footholds_kernel) return "plan_footholds"; if (p == (const void*)qm_episode_tick_kernel || p == (const void*)qm_episode_mpc_kernel || p == (const void*)qm_episode_start_kernel) return "episode";
+    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel || p == (const void*)(QmPolicyRolloutFn)qm_policy_rollout_kernel<QmFbStageView, SR_SIZE, false> || p == (const void*)(QmPolicyRolloutFn)qm_policy_rollout_kernel<QmFbPubView, PR_SIZE, true>) return "rollout"; if (p == (const void*)qm_sim_kernel || p == (const void*)qm_sim_push_kernel) return "sim"; if (p == (const void*)qm_sense_kernel) return "sense"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_policy_fb_kernel || p == (const void*)qm_policy_fb_pub_kernel) return "policy_fb"; if (p == (const void*)qm_policy_publish_kernel) return "publish"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io"; if (p == (const void*)qm_tick_state_kernel || p == (const void*)qm_tick_pack_kernel) return "tick"; if (p == (const void*)qm_plan_nodes_kernel) return "plan_nodes"; if (p == (const void*)qm_plan_states_kernel) return "plan_states"; if (p == (const void*)qm_plan_footholds_kernel) return "plan_footholds"; if (p == (const void*)qm_episode_tick_kernel || p == (const void*)qm_episode_mpc_kernel || p == (const void*)qm_episode_start_kernel) return "episode";
     return "ls_misc";
   }
   template <class K, class A> void launch(K kernel, int grid, int block, size_t lds, const A& args) {
@@ -820,6 +820,21 @@ int qmhip_sim_get_push(qmhip_ctx* c, int B, double* wrench, int32_t* mask) { QM_
   if (!c->sim.s.Bmax) { c->fail("qmhip_sim_get_push: neither qmhip_sim_reset nor qmhip_sim_set_pushes has been called"); return QMHIP_ERR_STATE; }
   hipSetDevice(c->device);
   if (wrench) c->bk.to_host(wrench, c->sim.s.push_out, (size_t)B * 9 * 8); if (mask) c->bk.to_host(mask, c->sim.s.push_mask, (size_t)B * 4);
+  return c->hipstate();
+}
+// sensor model (qmhip.h): the records of the measurement model between the plant and the controller, and what the controller is told
+int qmhip_sim_set_sensors(qmhip_ctx* c, int B, const qmhip_sensor* s) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c) return QMHIP_ERR_ARG;
+  if (s && (B <= 0 || B > c->max_batch)) { c->fail("qmhip_sim_set_sensors: bad argument (1 <= B <= max_batch)"); return QMHIP_ERR_ARG; }
+  if (s && !qm_sensors_valid(B, s)) { c->fail("qmhip_sim_set_sensors: a lag outside [0, QM_SENSE_MAX_LAG] or a negative / non-finite sigma / bias_sigma"); return QMHIP_ERR_ARG; }
+  hipSetDevice(c->device); c->sim.allocate(c->max_batch); c->sim.set_sensors(c->mpc.d.mb, B, s); return c->hipstate();
+}
+int qmhip_sim_get_measured(qmhip_ctx* c, int B, double* rbd, int32_t* samples) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c || B <= 0 || B > c->max_batch) { if (c) c->fail("qmhip_sim_get_measured: bad argument"); return QMHIP_ERR_ARG; }
+  if (!c->sim.s.Bmax) { c->fail("qmhip_sim_get_measured: qmhip_sim_reset has not been called"); return QMHIP_ERR_STATE; }
+  hipSetDevice(c->device);
+  if (rbd) c->bk.to_host(rbd, c->sim.meas_rbd(), (size_t)B * QM_NRBD * 8);
+  if (samples) { if (c->sim.s.sense_on) c->bk.to_host(samples, c->sim.s.sense_n, (size_t)B * 4); else for (int b = 0; b < B; ++b) samples[b] = 0; }
   return c->hipstate();
 }
 

@@ -1,6 +1,6 @@
 // k_loop.h — glue kernels of the device-resident control loop around the plant (SURVEY.md §8(f) rank 1 + 3), one thread per instance:
 //   qm_observe_kernel  QMController::updateStateEstimation (qm_controllers/src/QMController.cpp:202-244) with the "ground truth" estimator: the plant's rbd
-//                      state IS the measured state; currentObservation_.state = computeCentroidalStateFromRbdModel(rbd) [upstream ocs2_centroidal_model
+//                      state IS the measured state (or, with a sensor model set, k_sense.h's corruption of it); currentObservation_.state = computeCentroidalStateFromRbdModel(rbd) [upstream ocs2_centroidal_model
 //                      CentroidalModelRbdConversions, SRBD branch: normalized momentum = A_b(q) v_base / m], currentObservation_.time = plant time
 //   qm_command_kernel  QMController::updateControlLaw (QMController.cpp:177-190): legs setCommand(posDes, velDes, 0, 3, tau) once time > 10, arm
 //                      setCommand(posDes, 0, arm_kp_wbc, arm_kd_wbc, tau); posDes / velDes = joint part of the evaluated policy (QMController.cpp:156-157);
