@@ -399,6 +399,41 @@ int qmhip_sim_get_rbd(qmhip_ctx* ctx, int B, double* rbd /*[B][55]*/, int32_t* c
  *        active; either may be null.  Zeros after sim_reset and while pushes are off. */
 int qmhip_sim_set_pushes(qmhip_ctx* ctx, int B, int K, const qmhip_push* p /*[B][K]*/);
 int qmhip_sim_get_push(qmhip_ctx* ctx, int B, double* wrench /*[B][9]*/, int32_t* mask /*[B]*/);
+/* ---- plant terrain: a per-instance grid of ground heights and friction coefficients under the four feet, in place of the plane z = 0 with one global friction
+ *      coefficient.  The reference has no counterpart (its worlds are Gazebo's); the semantics are this library's own.  The MPC and the WBC keep their flat-floor
+ *      assumption: the terrain is what the blind controller is tested on.
+ *      sim_set_terrain: hdr is [B] records of struct qmhip_terrain, 32 bytes: qmhip_layout.h — vertex (i, j) of instance b lies at (x0 + i dx, y0 + j dy) in the world
+ *        frame —, height and mu are [B][ny][nx] with 2 <= nx, ny <= QM_TERRAIN_MAX, the same nx, ny for all instances of one call.  mu == NULL: the friction coefficient
+ *        of sim_set_params everywhere.  hdr == NULL switches the terrain off; sim_step and both closed loops then launch exactly the plant kernel they launch without the
+ *        feature.  With a terrain they launch qm_sim_terrain_kernel, or qm_sim_terrain_push_kernel while a schedule of pushes is set (one wavefront per instance, the
+ *        same LDS); the sensor kernel runs behind them as behind the other two.  The terrain persists across qmhip_sim_reset and may be set before the first one.  An
+ *        instance at or beyond B of a later, larger step stands on the plane z = 0 with the global friction coefficient.
+ *      LOOKUP at a point (x, y) — s = (x − x0) / dx; cx = (s < 0 or s > nx − 1); s = min(max(s, 0), nx − 1); i = min((int)floor(s), nx − 2); u = s − i, and t, cy, j, w
+ *        likewise in y.  With h00 = height[j][i], h10 = height[j][i + 1], h01 = height[j + 1][i], h11 = height[j + 1][i + 1]:
+ *          h  = (1 − w) ((1 − u) h00 + u h10) + w ((1 − u) h01 + u h11)            (mu: the same expression on the mu array)
+ *          gx = cx ? 0 : ((1 − w) (h10 − h00) + w (h11 − h01)) / dx
+ *          gy = cy ? 0 : ((1 − u) (h01 − h00) + u (h11 − h10)) / dy
+ *        Outside the grid the ground continues at the edge's height with zero slope along the clamped coordinate; at s == nx − 1 exactly the last cell's gradient holds.
+ *        The field is a continuous height map: no vertical faces, no overhangs.
+ *      CONTACT of foot f with centre p, velocity v and radius r = foot_radius against the tangent plane under its centre (h, gx, gy, mu looked up at (p_x, p_y)):
+ *          n   = (−gx, −gy, 1) / sqrt(1 + gx² + gy²)
+ *          pen = r − (p_z − h) n_z
+ *          vn  = v·n
+ *          fn  = pen > 0 ? max(0, k_n pen − d_n vn) : 0
+ *          vt  = v − vn n
+ *          f   = fn n − mu fn vt / sqrt(|vt|² + v_eps²)      (world frame; enters the dynamics through J_fᵀ f like the flat model's force)
+ *        The contact flag is pen > 0 at the handed-over state, the hand-over launch of sim_reset included.  With h = 0, gx = gy = 0 and mu the global coefficient this is
+ *        the flat model term for term.  Only the four feet touch the ground.
+ *      sim_get_ground: per foot (LF RF LH RH) {h, n_x, n_y, n_z, mu, pen} of the LAST sub-step of the last step, at the state that sub-step started from (like the contact
+ *        forces of sim_get_state).  Zeros after sim_reset and while the terrain is off.
+ *      terrain_eval: the plant's own lookup at n points per instance, xy[b][k] = (x, y), out[b][k] = {h, gx, gy, mu}; QMHIP_ERR_STATE without a terrain.
+ *      The episode monitor keeps the truth and is unchanged: its fall threshold min_base_z is an ABSOLUTE height, not a clearance above the ground, and its friction and
+ *        normal-force figures (max_friction_ratio, max_normal_force) use the world z axis — on sloped ground they are not cone margins.
+ *      sim_set_terrain returns QMHIP_ERR_ARG with nothing changed for B outside [1, max_batch], nx or ny outside [2, QM_TERRAIN_MAX], a non-finite header entry, dx or
+ *        dy <= 0, a non-finite height, a mu that is negative or non-finite; QMHIP_ERR_STATE on a WBC-only context. */
+int qmhip_sim_set_terrain(qmhip_ctx* ctx, int B, int nx, int ny, const qmhip_terrain* hdr /*[B], NULL: off*/, const double* height /*[B][ny][nx]*/, const double* mu /*same shape or NULL*/);
+int qmhip_sim_get_ground(qmhip_ctx* ctx, int B, double* ground /*[B][4][6]*/);
+int qmhip_terrain_eval(qmhip_ctx* ctx, int B, int n, const double* xy /*[B][n][2]*/, double* out /*[B][n][4]: h, gx, gy, mu*/);
 /* ---- sensor model: white noise, a constant bias and a latency of whole samples, per instance, on what the CONTROLLER is told about the plant.  The reference's simulation
  *      has only the "ground truth" estimator (FromTopiceEstimate); the semantics are this library's own.  The plant, qmhip_sim_step / qmhip_sim_get_rbd / _get_state and the
  *      episode monitor (fall check included) keep the truth; the MPC observation, the tick's state estimate, the WBC and updateControlLaw of both closed loops read the

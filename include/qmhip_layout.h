@@ -246,6 +246,12 @@ typedef struct qmhip_foothold { double time; int32_t leg, event; double pos[3]; 
 #define QM_PUSH_BYTES 96
 typedef struct qmhip_push { double t_on, t_off, base_force[3], base_torque[3], ee_force[3], spare; } qmhip_push;
 
+/* ground under one instance of the batched plant (qmhip.h, "plant terrain"; qmhip_sim_set_terrain takes [B] of them beside the height and friction arrays [B][ny][nx],
+   2 <= nx, ny <= QM_TERRAIN_MAX): vertex (i, j) of the grid lies at (x0 + i dx, y0 + j dy) in the world frame, dx, dy > 0 */
+#define QM_TERRAIN_MAX 16
+#define QM_TERRAIN_BYTES 32
+typedef struct qmhip_terrain { double x0, y0, dx, dy; } qmhip_terrain;
+
 /* sensor model of one instance of the batched plant (qmhip.h, "sensor model"; qmhip_sim_set_sensors takes [B] of them): what the controller is told is the plant's rbd
    state of `lag` samples ago plus, per group g of the rbd state (0 base zyx angles rbd[0:3], 1 base position [3:6], 2 joint positions [6:24], 3 base angular velocity
    [24:27], 4 base linear velocity [27:30], 5 joint rates [30:48]), a constant bias of standard deviation bias_sigma[g] and white noise of standard deviation sigma[g],
@@ -374,6 +380,7 @@ static_assert(offsetof(qmhip_plan_record, mode) == 8 * PT_MODE && offsetof(qmhip
               offsetof(qmhip_plan_record, ee_err) == 8 * PT_EE_ERR && offsetof(qmhip_plan_record, cop) == 8 * PT_COP && offsetof(qmhip_plan_record, spare) == 8 * PT_SPARE, "PT_* are the word offsets of qmhip_plan_record");
 static_assert(sizeof(qmhip_foothold) == QM_FOOTHOLD_BYTES && offsetof(qmhip_foothold, leg) == 8 && offsetof(qmhip_foothold, event) == 12 && offsetof(qmhip_foothold, pos) == 16, "qmhip_foothold is 40 bytes");
 static_assert(sizeof(qmhip_push) == QM_PUSH_BYTES && offsetof(qmhip_push, base_force) == 16 && offsetof(qmhip_push, base_torque) == 40 && offsetof(qmhip_push, ee_force) == 64 && offsetof(qmhip_push, spare) == 88, "qmhip_push is 12 doubles");
+static_assert(sizeof(qmhip_terrain) == QM_TERRAIN_BYTES && offsetof(qmhip_terrain, x0) == 0 && offsetof(qmhip_terrain, y0) == 8 && offsetof(qmhip_terrain, dx) == 16 && offsetof(qmhip_terrain, dy) == 24, "qmhip_terrain is 4 doubles");
 static_assert(sizeof(qmhip_sensor) == QM_SENSE_BYTES && offsetof(qmhip_sensor, seed) == 0 && offsetof(qmhip_sensor, lag) == 8 && offsetof(qmhip_sensor, spare0) == 12 && offsetof(qmhip_sensor, sigma) == 16 &&
               offsetof(qmhip_sensor, bias_sigma) == 16 + 8 * QM_SENSE_GROUPS && offsetof(qmhip_sensor, spare) == 16 + 16 * QM_SENSE_GROUPS, "qmhip_sensor is 16 eight-byte words");
 #endif

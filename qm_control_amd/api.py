@@ -30,6 +30,7 @@ EXPORTS = ["qmhip_create", "qmhip_create_from_blobs", "qmhip_create_wbc_context"
            "qmhip_plan_task_space", "qmhip_plan_footholds", "qmhip_task_space_eval", "qmhip_policy_rollout",
            "qmhip_episode_monitor", "qmhip_episode_set_anchor", "qmhip_episode_summary", "qmhip_episode_trace", "qmhip_episode_fold",
            "qmhip_tick_reset", "qmhip_tick_submit", "qmhip_tick_collect", "qmhip_observe", "qmhip_sim_get_rbd", "qmhip_sim_set_pushes", "qmhip_sim_get_push", "qmhip_sim_set_sensors", "qmhip_sim_get_measured",
+           "qmhip_sim_set_terrain", "qmhip_sim_get_ground", "qmhip_terrain_eval",
            "qmhip_sim_set_params", "qmhip_sim_set_controller", "qmhip_sim_reset", "qmhip_sim_set_command", "qmhip_sim_step", "qmhip_sim_get_state", "qmhip_closed_loop_sim", "qmhip_closed_loop_sim_pipelined"]
 
 # struct qmhip_step_record (include/qmhip_layout.h) as a numpy structured dtype: one 1024-byte record per instance and control step
@@ -51,6 +52,9 @@ EPISODE_SAMPLE = _rec_dtype(L.EPISODE_SAMPLE_FIELDS, L.QM_ES_BYTES)
 # struct qmhip_push: one scheduled external wrench on the plant, 96 bytes (QMHWSim.set_pushes)
 PUSH = _rec_dtype(L.PUSH_FIELDS, L.QM_PUSH_BYTES)
 SIM_MAX_PUSH = L.QM_SIM_MAX_PUSH
+# struct qmhip_terrain: origin and spacing of one instance's ground grid, 32 bytes (QMHWSim.set_terrain)
+TERRAIN = _rec_dtype(L.TERRAIN_FIELDS, L.QM_TERRAIN_BYTES)
+TERRAIN_MAX = L.QM_TERRAIN_MAX
 # struct qmhip_sensor: the sensor model of one instance of the plant, 128 bytes (QMHWSim.set_sensors)
 SENSOR = _rec_dtype(L.SENSOR_FIELDS, L.QM_SENSE_BYTES)
 SENSE_MAX_LAG, SENSE_GROUPS = L.QM_SENSE_MAX_LAG, L.QM_SENSE_GROUPS
@@ -541,6 +545,29 @@ class QMHWSim:
         B = self.B if B is None else int(B); w = np.zeros((B, 9)); m = np.zeros(B, np.int32)
         self.itf._check(self.lib.qmhip_sim_get_push(self.itf.h, B, _p(w), _pi(m)), "qmhip_sim_get_push")
         return w, m
+
+    def set_terrain(self, hdr, height=None, mu=None):
+        """ground under the feet (qmhip_sim_set_terrain): hdr is [B] of dtype TERRAIN (x0, y0, dx, dy of each instance's grid in the world frame), height [B][ny][nx] and
+        mu (same shape, or None: the `friction` of set_params everywhere) with 2 <= nx, ny <= TERRAIN_MAX.  Bilinear between the vertices, continued at the edge's height
+        outside; every foot meets the tangent plane under it.  set_terrain(None) puts the plant back on the plane z = 0.  The terrain persists across reset()"""
+        if hdr is None:
+            self.itf._check(self.lib.qmhip_sim_set_terrain(self.itf.h, 0, 0, 0, None, None, None), "qmhip_sim_set_terrain"); return
+        hdr = np.ascontiguousarray(hdr, dtype=TERRAIN); height = _f(height); mu = None if mu is None else _f(mu)
+        assert hdr.ndim == 1 and height.ndim == 3 and height.shape[0] == hdr.shape[0] and (mu is None or mu.shape == height.shape)
+        self.itf._check(self.lib.qmhip_sim_set_terrain(self.itf.h, hdr.shape[0], height.shape[2], height.shape[1], hdr.ctypes.data_as(C.c_void_p), _p(height), _p(mu)), "qmhip_sim_set_terrain")
+
+    def ground(self, B=None):
+        """[B][4][6]: per foot (LF RF LH RH) h, n_x, n_y, n_z, mu, pen of the last sub-step of the last step — zeros after reset() and without a terrain"""
+        B = self.B if B is None else int(B); g = np.zeros((B, 4, 6))
+        self.itf._check(self.lib.qmhip_sim_get_ground(self.itf.h, B, _p(g)), "qmhip_sim_get_ground")
+        return g
+
+    def terrain_eval(self, xy):
+        """the plant's lookup at xy [B][n][2] (world frame): [B][n][4] = h, gx, gy, mu"""
+        xy = _f(xy); assert xy.ndim == 3 and xy.shape[2] == 2
+        out = np.zeros(xy.shape[:2] + (4,))
+        self.itf._check(self.lib.qmhip_terrain_eval(self.itf.h, xy.shape[0], xy.shape[1], _p(xy), _p(out)), "qmhip_terrain_eval")
+        return out
 
     def set_sensors(self, s):
         """sensor model between the plant and the controller (qmhip_sim_set_sensors): s is [B] of dtype SENSOR — per instance a seed, a latency `lag` of whole samples

@@ -20,6 +20,9 @@ struct QmSimBuffers {
   double* push = nullptr; int push_K = 0, push_B = 0; double* push_out = nullptr; int* push_mask = nullptr;
   // sensor model (qmhip_sim_set_sensors): the records [sense_B] of struct qmhip_sensor (sense_on false: off, nothing of k_sense.h is launched and the controller reads rbd),
   // the truth of the last samples [Bmax][QM_SENSE_SLOTS][55], the index of the last sample [Bmax], what the controller is told [Bmax][55]; plant_B: batch of the last reset
+  // terrain (qmhip_sim_set_terrain): headers [ter_B] of struct qmhip_terrain, heights and friction [ter_B][ter_ny][ter_nx] — allocated by the first set_terrain for Bmax
+  // instances of QM_TERRAIN_MAX² vertices (ter_on false: the plane z = 0, the plant kernels without terrain run) — and the per-foot ground records [Bmax][4][6]
+  double* ter_hdr = nullptr; double* ter_h = nullptr; double* ter_mu = nullptr; bool ter_on = false, ter_has_mu = false; int ter_B = 0, ter_nx = 0, ter_ny = 0; double* ground = nullptr;
   unsigned long long* sense = nullptr; bool sense_on = false; int sense_B = 0; double* sense_ring = nullptr; int* sense_n = nullptr; double* rbd_meas = nullptr; int plant_B = 0;
 };
 
@@ -31,6 +34,19 @@ inline bool qm_pushes_valid(int B, int K, const double* p) {
     if (r[0] != r[0] || r[1] != r[1]) return false;
     for (int j = 2; j < 11; ++j) if (!(r[j] - r[j] == 0.0)) return false;      // inf - inf and NaN - NaN are NaN
   }
+  return true;
+}
+
+// what qmhip_sim_set_terrain accepts: 2 <= nx, ny <= QM_TERRAIN_MAX, finite headers with dx, dy > 0, finite heights, friction coefficients that are finite and not negative
+static_assert(sizeof(qmhip_terrain) == QM_TERRAIN_WORDS * 8, "the plant kernel reads struct qmhip_terrain as QM_TERRAIN_WORDS doubles");
+inline bool qm_terrain_valid(int B, int nx, int ny, const qmhip_terrain* hdr, const double* height, const double* mu) {
+  if (nx < 2 || ny < 2 || nx > QM_TERRAIN_MAX || ny > QM_TERRAIN_MAX || !height) return false;
+  for (int b = 0; b < B; ++b) {
+    const double r[4] = {hdr[b].x0, hdr[b].y0, hdr[b].dx, hdr[b].dy};
+    for (int j = 0; j < 4; ++j) if (!(r[j] - r[j] == 0.0)) return false;
+    if (!(r[2] > 0.0 && r[3] > 0.0)) return false;
+  }
+  for (size_t i = 0; i < (size_t)B * ny * nx; ++i) { if (!(height[i] - height[i] == 0.0)) return false; if (mu && !(mu[i] >= 0.0 && mu[i] - mu[i] == 0.0)) return false; }
   return true;
 }
 
@@ -57,21 +73,41 @@ struct QmSimPipeline {
     s.force = A<double>((size_t)Bmax * 12); s.status = A<int>(Bmax);
     s.arm_hold = A<double>((size_t)Bmax * 6); s.arm_last = A<double>((size_t)Bmax * 6); s.x_est = A<double>((size_t)Bmax * 30); s.t_est = A<double>(Bmax);
     s.push = A<double>((size_t)Bmax * QM_SIM_MAX_PUSH * QM_PUSH_WORDS); s.push_out = A<double>((size_t)Bmax * 9); s.push_mask = A<int>(Bmax);
+    s.ground = A<double>((size_t)Bmax * 24);
     s.sense = A<unsigned long long>((size_t)Bmax * QM_SENSE_WORDS); s.sense_ring = A<double>((size_t)Bmax * QM_SENSE_SLOTS * QM_NRBD); s.sense_n = A<int>(Bmax); s.rbd_meas = A<double>((size_t)Bmax * QM_NRBD);
   }
-  void release() { void* ps[] = {s.q, s.v, s.time, s.cmd, s.ring, s.ring_n, s.rbd, s.contact, s.force, s.status, s.arm_hold, s.arm_last, s.p_xs, s.p_us, s.p_node_t, s.p_node_ev, s.p_n_nodes, s.p_ev, s.p_modes, s.x_est, s.t_est, s.push, s.push_out, s.push_mask, s.sense, s.sense_ring, s.sense_n, s.rbd_meas}; for (void* ptr : ps) if (ptr) bk.free(ptr); s = QmSimBuffers(); }
+  void release() { void* ps[] = {s.q, s.v, s.time, s.cmd, s.ring, s.ring_n, s.rbd, s.contact, s.force, s.status, s.arm_hold, s.arm_last, s.p_xs, s.p_us, s.p_node_t, s.p_node_ev, s.p_n_nodes, s.p_ev, s.p_modes, s.x_est, s.t_est, s.push, s.push_out, s.push_mask, s.sense, s.sense_ring, s.sense_n, s.rbd_meas, s.ter_hdr, s.ter_h, s.ter_mu, s.ground}; for (void* ptr : ps) if (ptr) bk.free(ptr); s = QmSimBuffers(); }
   // "Simulation reset" of QMHWSim::writeSim: state set, delay buffer and held command cleared
   void reset(int B, const double* q_host, const double* v_host, const double* time_host) {
     s.p_valid = false; s.plant_B = B;
     bk.to_device(s.q, q_host, (size_t)B * 24 * 8); bk.to_device(s.v, v_host, (size_t)B * 24 * 8); bk.to_device(s.time, time_host, (size_t)B * 8);
     bk.zero(s.ring_n, (size_t)s.Bmax * 2 * sizeof(int)); bk.zero(s.cmd, (size_t)s.Bmax * (QM_SIM_CMD - 1) * 8);
     bk.zero(s.push_out, (size_t)s.Bmax * 9 * 8); bk.zero(s.push_mask, (size_t)s.Bmax * sizeof(int));      // nothing applied yet; the schedule itself (absolute plant time) stays
+    bk.zero(s.ground, (size_t)s.Bmax * 24 * 8);      // no sub-step yet; the terrain itself stays
     QmArmResetArgs r; r.B = B; r.q = s.q; r.time = s.time; r.arm_hold = s.arm_hold; r.arm_last = s.arm_last; bk.launch(qm_arm_reset_kernel, (B * 6 + 63) / 64, 64, 0, r);
   }
   // schedule of external wrenches, [B][K] records of QM_PUSH_WORDS doubles (validated by the caller); K = 0 or a null pointer switches them off
   void set_pushes(int B, int K, const double* host) {
     if (K <= 0 || !host) { s.push_K = 0; s.push_B = 0; bk.zero(s.push_out, (size_t)s.Bmax * 9 * 8); bk.zero(s.push_mask, (size_t)s.Bmax * sizeof(int)); return; }
     bk.to_device(s.push, host, (size_t)B * K * QM_PUSH_WORDS * 8); s.push_K = K; s.push_B = B;
+  }
+  // ground of B instances (validated by the caller), a null header switches the terrain off.  The three buffers are sized for Bmax instances of the largest grid on the
+  // first call (32 MB at Bmax = 8192: not worth holding for a plant that never leaves the plane)
+  void set_terrain(int B, int nx, int ny, const qmhip_terrain* hdr, const double* height, const double* mu) {
+    if (!hdr) { s.ter_on = false; s.ter_has_mu = false; s.ter_B = 0; bk.zero(s.ground, (size_t)s.Bmax * 24 * 8); return; }
+    const size_t cap = (size_t)s.Bmax * QM_TERRAIN_MAX * QM_TERRAIN_MAX, n = (size_t)B * ny * nx;
+    if (!s.ter_h) { s.ter_hdr = A<double>((size_t)s.Bmax * QM_TERRAIN_WORDS); s.ter_h = A<double>(cap); s.ter_mu = A<double>(cap); }
+    bk.to_device(s.ter_hdr, hdr, (size_t)B * QM_TERRAIN_BYTES); bk.to_device(s.ter_h, height, n * 8); if (mu) bk.to_device(s.ter_mu, mu, n * 8);
+    s.ter_on = true; s.ter_has_mu = mu != nullptr; s.ter_B = B; s.ter_nx = nx; s.ter_ny = ny;
+  }
+  QmTerrainArgs terrain_args() const { QmTerrainArgs t; t.hdr = s.ter_hdr; t.nx = s.ter_nx; t.ny = s.ter_ny; t.nB = s.ter_B; t.height = s.ter_h; t.mu = s.ter_has_mu ? s.ter_mu : nullptr; t.ground = s.ground; return t; }
+  // the plant's lookup at n points per instance (host arrays; a terrain is set — the caller checks)
+  void terrain_eval(int B, int n, const double* xy_host, double* out_host) {
+    const size_t N = (size_t)B * n; double* xy = (double*)bk.alloc(N * 2 * 8); double* out = (double*)bk.alloc(N * 4 * 8);
+    bk.to_device(xy, xy_host, N * 2 * 8);
+    QmTerrainEvalArgs e; e.ter = terrain_args(); e.B = B; e.n = n; e.mu_default = p.mu; e.xy = xy; e.out = out;
+    bk.launch(qm_terrain_eval_kernel, (int)((N + 63) / 64), 64, 0, e);
+    bk.to_host(out_host, out, N * 4 * 8); bk.free(xy); bk.free(out);
   }
   // sensor records [B] (validated by the caller), a null pointer switches the model off.  The sample count starts over: a plant that has been reset hands sample 0 over
   // from its current state at once (one launch of the sensor kernel, none of the plant)
@@ -110,6 +146,12 @@ struct QmSimPipeline {
   void step(const double* mb_dev, int B, double period, int nsub) {
     QmSimArgs a; a.mb = mb_dev; a.B = B; a.nsub = nsub; a.h = nsub > 0 ? period / nsub : 0.0; a.p = p; a.q = s.q; a.v = s.v; a.time = s.time; a.cmd = s.cmd; a.ring = s.ring; a.ring_n = s.ring_n;
     a.rbd = s.rbd; a.contact = s.contact; a.force = s.force; a.status = s.status;
+    if (s.ter_on) {                                      // a terrain is set: the two instances of the kernel that look the ground up
+      if (s.push_K > 0) {
+        QmSimTerrainPushArgs ta; ta.sim = a; ta.push.push = s.push; ta.push.K = s.push_K; ta.push.nB = s.push_B; ta.push.push_out = s.push_out; ta.push.push_mask = s.push_mask; ta.ter = terrain_args();
+        bk.launch(qm_sim_terrain_push_kernel, B, 64, SIM_LDS_BYTES, ta);
+      } else { QmSimTerrainArgs ta; ta.sim = a; ta.ter = terrain_args(); bk.launch(qm_sim_terrain_kernel, B, 64, SIM_LDS_BYTES, ta); }
+    } else
     if (s.push_K > 0) {                                  // a schedule is set: the instance of the kernel that applies it
       QmSimPushArgs pa; pa.sim = a; pa.push.push = s.push; pa.push.K = s.push_K; pa.push.nB = s.push_B; pa.push.push_out = s.push_out; pa.push.push_mask = s.push_mask;
       bk.launch(qm_sim_push_kernel, B, 64, SIM_LDS_BYTES, pa);

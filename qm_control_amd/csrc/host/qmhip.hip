@@ -53,7 +53,7 @@ struct HipBackend {
     const void* p = (const void*)k;
     if (p == (const void*)qm_grid_kernel || p == (const void*)qm_grid_nodes_kernel || p == (const void*)qm_save_grid_kernel || p == (const void*)qm_advance_kernel) return "grid"; if (p == (const void*)qm_lq_kernel || p == (const void*)qm_lq_dbg_kernel || p == (const void*)qm_lq_ipm_kernel) return "lq"; if (p == (const void*)qm_lq_m18_kernel) return "lq_m18"; if (p == (const void*)qm_lq_kin_kernel) return "lq_kin"; if (p == (const void*)qm_riccati_kernel || p == (const void*)qm_riccati_prof_kernel) return "riccati";
     if (p == (const void*)qm_ls_eval_kernel || p == (const void*)qm_ls_eval_dense_kernel || p == (const void*)qm_ls_eval_ipm_kernel) return "ls_eval";
-    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel || p == (const void*)(QmPolicyRolloutFn)qm_policy_rollout_kernel<QmFbStageView, SR_SIZE, false> || p == (const void*)(QmPolicyRolloutFn)qm_policy_rollout_kernel<QmFbPubView, PR_SIZE, true>) return "rollout"; if (p == (const void*)qm_sim_kernel || p == (const void*)qm_sim_push_kernel) return "sim"; if (p == (const void*)qm_sense_kernel) return "sense"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_policy_fb_kernel || p == (const void*)qm_policy_fb_pub_kernel) return "policy_fb"; if (p == (const void*)qm_policy_publish_kernel) return "publish"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io"; if (p == (const void*)qm_tick_state_kernel || p == (const void*)qm_tick_pack_kernel) return "tick"; if (p == (const void*)qm_plan_nodes_kernel) return "plan_nodes"; if (p == (const void*)qm_plan_states_kernel) return "plan_states"; if (p == (const void*)qm_plan_footholds_kernel) return "plan_footholds"; if (p == (const void*)qm_episode_tick_kernel || p == (const void*)qm_episode_mpc_kernel || p == (const void*)qm_episode_start_kernel) return "episode";
+    if (p == (const void*)qm_ipm_init_kernel || p == (const void*)qm_ipm_dir_kernel || p == (const void*)qm_ipm_alpha_kernel || p == (const void*)qm_ipm_commit_kernel || p == (const void*)qm_ipm_barrier_kernel) return "ipm"; if (p == (const void*)qm_ilqr_rollout_kernel || p == (const void*)(QmPolicyRolloutFn)qm_policy_rollout_kernel<QmFbStageView, SR_SIZE, false> || p == (const void*)(QmPolicyRolloutFn)qm_policy_rollout_kernel<QmFbPubView, PR_SIZE, true>) return "rollout"; if (p == (const void*)qm_sim_kernel || p == (const void*)qm_sim_push_kernel || p == (const void*)qm_sim_terrain_kernel || p == (const void*)qm_sim_terrain_push_kernel) return "sim"; if (p == (const void*)qm_terrain_eval_kernel) return "terrain_eval"; if (p == (const void*)qm_sense_kernel) return "sense"; if (p == (const void*)qm_wbc_kernel || p == (const void*)qm_wbc_prof_kernel) return "wbc"; if (p == (const void*)qm_policy_kernel || p == (const void*)qm_policy_measured_kernel) return "policy"; if (p == (const void*)qm_policy_fb_kernel || p == (const void*)qm_policy_fb_pub_kernel) return "policy_fb"; if (p == (const void*)qm_policy_publish_kernel) return "publish"; if (p == (const void*)qm_hoqp_kernel) return "hoqp"; if (p == (const void*)qm_step_pack_kernel) return "io"; if (p == (const void*)qm_tick_state_kernel || p == (const void*)qm_tick_pack_kernel) return "tick"; if (p == (const void*)qm_plan_nodes_kernel) return "plan_nodes"; if (p == (const void*)qm_plan_states_kernel) return "plan_states"; if (p == (const void*)qm_plan_footholds_kernel) return "plan_footholds"; if (p == (const void*)qm_episode_tick_kernel || p == (const void*)qm_episode_mpc_kernel || p == (const void*)qm_episode_start_kernel) return "episode";
     return "ls_misc";
   }
   template <class K, class A> void launch(K kernel, int grid, int block, size_t lds, const A& args) {
@@ -821,6 +821,25 @@ int qmhip_sim_get_push(qmhip_ctx* c, int B, double* wrench, int32_t* mask) { QM_
   hipSetDevice(c->device);
   if (wrench) c->bk.to_host(wrench, c->sim.s.push_out, (size_t)B * 9 * 8); if (mask) c->bk.to_host(mask, c->sim.s.push_mask, (size_t)B * 4);
   return c->hipstate();
+}
+// plant terrain (qmhip.h): the per-robot ground grids the next steps of the plant stand on, the ground records of the last sub-step, the lookup itself
+int qmhip_sim_set_terrain(qmhip_ctx* c, int B, int nx, int ny, const qmhip_terrain* hdr, const double* height, const double* mu) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c) return QMHIP_ERR_ARG;
+  if (hdr && (B <= 0 || B > c->max_batch)) { c->fail("qmhip_sim_set_terrain: bad argument (1 <= B <= max_batch)"); return QMHIP_ERR_ARG; }
+  if (hdr && !qm_terrain_valid(B, nx, ny, hdr, height, mu)) { c->fail("qmhip_sim_set_terrain: nx / ny outside [2, QM_TERRAIN_MAX], a non-finite header entry, dx / dy <= 0, a non-finite height or a negative / non-finite mu"); return QMHIP_ERR_ARG; }
+  hipSetDevice(c->device); c->sim.allocate(c->max_batch); c->sim.set_terrain(B, nx, ny, hdr, height, mu); return c->hipstate();
+}
+int qmhip_sim_get_ground(qmhip_ctx* c, int B, double* ground) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c || B <= 0 || B > c->max_batch) { if (c) c->fail("qmhip_sim_get_ground: bad argument"); return QMHIP_ERR_ARG; }
+  if (!c->sim.s.Bmax) { c->fail("qmhip_sim_get_ground: neither qmhip_sim_reset nor qmhip_sim_set_terrain has been called"); return QMHIP_ERR_STATE; }
+  hipSetDevice(c->device);
+  if (ground) c->bk.to_host(ground, c->sim.s.ground, (size_t)B * 24 * 8);
+  return c->hipstate();
+}
+int qmhip_terrain_eval(qmhip_ctx* c, int B, int n, const double* xy, double* out) { QM_GUARD(c); QM_NEED_MPC(c);
+  if (!c || B <= 0 || B > c->max_batch || n <= 0 || !xy || !out) { if (c) c->fail("qmhip_terrain_eval: bad argument"); return QMHIP_ERR_ARG; }
+  if (!c->sim.s.ter_on) { c->fail("qmhip_terrain_eval: no terrain is set (qmhip_sim_set_terrain)"); return QMHIP_ERR_STATE; }
+  hipSetDevice(c->device); c->bk.cur = c->bk.stream; c->sim.terrain_eval(B, n, xy, out); return c->hipstate();
 }
 // sensor model (qmhip.h): the records of the measurement model between the plant and the controller, and what the controller is told
 int qmhip_sim_set_sensors(qmhip_ctx* c, int B, const qmhip_sensor* s) { QM_GUARD(c); QM_NEED_MPC(c);

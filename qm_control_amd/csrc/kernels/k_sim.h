@@ -17,6 +17,8 @@
 //     "ground truth" estimator (FromTopiceEstimate).
 //   * external wrenches (no counterpart in the reference's sources): qm_sim_push_kernel, the second instance of the step's body, applies a schedule of base forces,
 //     base torques and end-effector forces (QmPushArgs); qm_sim_kernel is the instance without them.
+//   * terrain (no counterpart in the reference's sources): qm_sim_terrain_kernel / qm_sim_terrain_push_kernel, two further instances of the step's body, put every foot
+//     on a per-robot grid of heights and friction coefficients (QmTerrainArgs; the model: qmhip.h "plant terrain") instead of the plane z = 0.
 // Joint position limits and self collision are not modelled.
 #pragma once
 #include "qm_dev_rbd.h"
@@ -46,6 +48,34 @@ struct QmPushArgs {
   int* push_mask;                       // [B] bit k: slot k was active in the last sub-step
 };
 struct QmSimPushArgs { QmSimArgs sim; QmPushArgs push; };      // (one argument record per launch: the backends' launch() takes one)
+// per-robot ground (struct qmhip_terrain, qmhip_layout.h; the model: qmhip.h "plant terrain"): ny x nx vertices of height and friction in the world frame
+#define QM_TERRAIN_WORDS (QM_TERRAIN_BYTES / 8)   /* x0, y0, dx, dy */
+struct QmTerrainArgs {
+  const double* hdr; int nx, ny, nB;    // [nB][QM_TERRAIN_WORDS] grid origin and spacing; 2 <= nx, ny <= QM_TERRAIN_MAX; instances at or beyond nB stand on the plane z = 0 with p.mu
+  const double* height;                 // [nB][ny][nx]
+  const double* mu;                     // [nB][ny][nx], or null: p.mu everywhere
+  double* ground;                       // [B][4][6] per foot h, n_x, n_y, n_z, mu, pen of the last sub-step
+};
+struct QmSimTerrainArgs { QmSimArgs sim; QmTerrainArgs ter; };
+struct QmSimTerrainPushArgs { QmSimArgs sim; QmPushArgs push; QmTerrainArgs ter; };
+
+// ---- the grid lookup, shared by the plant instances and qm_terrain_eval_kernel.  The cell of a point: clamped to the grid (beyond it the ground continues at the edge's
+//      height with zero slope along the clamped coordinate), at s == nx - 1 exactly the last cell ----
+struct QmTerrainCell { int i, j; double u, w; bool cx, cy; };
+__device__ __forceinline__ void qm_terrain_axis(double x, double x0, double dx, int n, int& i, double& u, bool& c) {
+  double s = (x - x0) / dx; c = (s < 0.0 || s > (double)(n - 1)); s = fmin(fmax(s, 0.0), (double)(n - 1));      // (fmax / fmin: a NaN coordinate lands on vertex 0, never outside the array)
+  const int k = (int)floor(s); i = k < n - 2 ? k : n - 2; u = s - (double)i;
+}
+__device__ __forceinline__ QmTerrainCell qm_terrain_cell(const double* hdr, int nx, int ny, double x, double y) {
+  QmTerrainCell c; qm_terrain_axis(x, hdr[0], hdr[2], nx, c.i, c.u, c.cx); qm_terrain_axis(y, hdr[1], hdr[3], ny, c.j, c.w, c.cy); return c;
+}
+// corner k = 0..3 of the cell is vertex (i + (k & 1), j + (k >> 1)): 00, 10, 01, 11
+__device__ __forceinline__ size_t qm_terrain_corner(const QmTerrainCell& c, int nx, int k) { return (size_t)(c.j + (k >> 1)) * nx + (size_t)(c.i + (k & 1)); }
+__device__ __forceinline__ double qm_terrain_blend(const QmTerrainCell& c, const double* k4) { return (1.0 - c.w) * ((1.0 - c.u) * k4[0] + c.u * k4[1]) + c.w * ((1.0 - c.u) * k4[2] + c.u * k4[3]); }
+__device__ __forceinline__ void qm_terrain_slope(const QmTerrainCell& c, const double* hdr, const double* h4, double& gx, double& gy) {
+  gx = c.cx ? 0.0 : ((1.0 - c.w) * (h4[1] - h4[0]) + c.w * (h4[3] - h4[2])) / hdr[2];
+  gy = c.cy ? 0.0 : ((1.0 - c.u) * (h4[2] - h4[0]) + c.u * (h4[3] - h4[1])) / hdr[3];
+}
 
 // ---- LDS carve (doubles) ----
 #define SL_M     0                      /* [24][24] */
@@ -62,6 +92,7 @@ struct QmSimPushArgs { QmSimArgs sim; QmPushArgs push; };      // (one argument 
 #define SL_COMP  1290                   /* [19 x 6][6] per-joint subtree composites of the six chain lanes (lane interleaved; registers would spill) */
 #define SL_TOTAL (SL_COMP + 19 * 6 * 6)
 #define SIM_LDS_BYTES (SL_TOTAL * 8)
+#define SL_TER   (SL_ACC + 16)          /* terrain instances: [2][16] corner heights and friction of the four feet (the accumulators are free between two calls of sim_dynamics_terms) */
 
 // measured pass of one chain per lane (lanes 0-3 legs, 4 arm, 5 root body) + base block: M, nle, foot Jacobians, tips
 // PUSH: the arm lane keeps its tip Jacobian too — SL_JDUM is zeroed and then holds [lin(3); ang(3)][24], the linear rows with their base columns (the rows J_ee of an
@@ -114,8 +145,33 @@ __device__ __forceinline__ void sim_dynamics_terms(const double* mb, double* S, 
   qm_wave_sync();
 }
 
-template <bool PUSH>
-__device__ __forceinline__ void sim_step_body(const QmSimArgs& a, const QmPushArgs& pa) {
+// ground under the four feet at the tips of SL_TIP: ONE round of loads, lane 4 f + c fetches corner c of foot f from both arrays into SL_TER; lanes f < 4 then combine
+// their four corners in the stated order.  Every lane of the wave calls it.  g = {h, gx, gy, mu} on lanes 0-3
+__device__ __forceinline__ void sim_ground(const QmSimArgs& a, const QmTerrainArgs& ta, double* S, const int b, const int l, double* g) {
+  const bool has = b < ta.nB; const double* hdr = ta.hdr + (size_t)(has ? b : 0) * QM_TERRAIN_WORDS;
+  if (has && l < 16) {
+    const double* tp = S + SL_TIP + 6 * (l >> 2); const QmTerrainCell c = qm_terrain_cell(hdr, ta.nx, ta.ny, tp[0], tp[1]);
+    const size_t at = (size_t)b * ta.ny * ta.nx + qm_terrain_corner(c, ta.nx, l & 3);
+    S[SL_TER + l] = ta.height[at]; if (ta.mu) S[SL_TER + 16 + l] = ta.mu[at];
+  }
+  qm_wave_sync();
+  if (l < 4) {
+    g[0] = 0.0; g[1] = 0.0; g[2] = 0.0; g[3] = a.p.mu;
+    if (has) {
+      const double* tp = S + SL_TIP + 6 * l; const QmTerrainCell c = qm_terrain_cell(hdr, ta.nx, ta.ny, tp[0], tp[1]);
+      g[0] = qm_terrain_blend(c, S + SL_TER + 4 * l); qm_terrain_slope(c, hdr, S + SL_TER + 4 * l, g[1], g[2]);
+      if (ta.mu) g[3] = qm_terrain_blend(c, S + SL_TER + 16 + 4 * l);
+    }
+  }
+}
+// tangent plane under a foot: unit normal n and penetration of the sphere of radius r at centre height pz
+__device__ __forceinline__ double sim_ground_pen(const double* g, double r, double pz, double* n) {
+  const double sq = sqrt(1.0 + g[1] * g[1] + g[2] * g[2]); n[0] = -g[1] / sq; n[1] = -g[2] / sq; n[2] = 1.0 / sq;
+  return r - (pz - g[0]) * n[2];
+}
+
+template <bool PUSH, bool TERRAIN>
+__device__ __forceinline__ void sim_step_body(const QmSimArgs& a, const QmPushArgs& pa, const QmTerrainArgs& ta) {
   extern __shared__ double qm_smem[];
   double* S = qm_smem;
   const int b = blockIdx.x, l = threadIdx.x & 63;
@@ -128,6 +184,7 @@ __device__ __forceinline__ void sim_step_body(const QmSimArgs& a, const QmPushAr
   double* ring = a.ring + (size_t)b * QM_SIM_SLOTS * QM_SIM_CMD;
   int bad = 0;
   double pw = 0.0; int pmask = 0;         // PUSH: lane l < 9 keeps component l of the applied wrench (base force, base torque, end-effector force); active slots
+  double gr[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // TERRAIN: lane l < 4 keeps its foot's ground record of the last sub-step (nsub == 0: zeros)
   qm_wave_sync();
   // ---- delay buffer (QMHWSim.cpp:100-110), once per call like writeSim once per simulation step: drop what is older than `delay`, push the held
   //      command with the current time stamp, apply the oldest survivor during this step ----
@@ -156,7 +213,21 @@ __device__ __forceinline__ void sim_step_body(const QmSimArgs& a, const QmPushAr
       if (a.p.saturate) t = fmin(tm, fmax(-tm, t));
       tau[j] = t;
     }
-    if (l < 4) {
+    if constexpr (TERRAIN) {              // contact against the tangent plane of the ground under the foot
+      double g[4]; sim_ground(a, ta, S, b, l, g);
+      if (l < 4) {
+        const double* tp = S + SL_TIP + 6 * l; double n[3]; const double pen = sim_ground_pen(g, a.p.foot_radius, tp[2], n);
+        double fx = 0.0, fy = 0.0, fz = 0.0;
+        if (pen > 0.0) {
+          const double vn = tp[3] * n[0] + tp[4] * n[1] + tp[5] * n[2]; const double fn = fmax(0.0, a.p.k_n * pen - a.p.d_n * vn);
+          const double vt[3] = {tp[3] - vn * n[0], tp[4] - vn * n[1], tp[5] - vn * n[2]};
+          const double sc = -g[3] * fn / sqrt(vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2] + a.p.v_eps * a.p.v_eps);
+          fx = fn * n[0] + sc * vt[0]; fy = fn * n[1] + sc * vt[1]; fz = fn * n[2] + sc * vt[2];
+        }
+        fc[3 * l] = fx; fc[3 * l + 1] = fy; fc[3 * l + 2] = fz;
+        gr[0] = g[0]; gr[1] = n[0]; gr[2] = n[1]; gr[3] = n[2]; gr[4] = g[3]; gr[5] = pen;
+      }
+    } else if (l < 4) {
       const double* tp = S + SL_TIP + 6 * l; const double pen = a.p.foot_radius - tp[2];
       double fx = 0.0, fy = 0.0, fz = 0.0;
       if (pen > 0.0) {
@@ -207,12 +278,33 @@ __device__ __forceinline__ void sim_step_body(const QmSimArgs& a, const QmPushAr
   if (l == 3) { double E[9]; euler_E(q[3], q[4], E); const double thd[3] = {v[3], v[4], v[5]}; double w[3]; m3_mulv(E, thd, w); for (int i = 0; i < 3; ++i) r[24 + i] = w[i]; }
   if (l >= 6 && l < 24) { r[l] = q[l]; r[24 + l] = v[l]; }
   if (l == 4) { double qq[4]; mat_to_quat(S + SL_TIP + 27, qq); for (int i = 0; i < 3; ++i) r[48 + i] = S[SL_TIP + 24 + i]; for (int i = 0; i < 4; ++i) r[51 + i] = qq[i]; }
+  if constexpr (TERRAIN) {
+    double g[4]; sim_ground(a, ta, S, b, l, g);
+    if (l < 4) { double n[3]; a.contact[b * 4 + l] = (sim_ground_pen(g, a.p.foot_radius, S[SL_TIP + 6 * l + 2], n) > 0.0) ? 1 : 0;
+      for (int i = 0; i < 6; ++i) ta.ground[(size_t)b * 24 + 6 * l + i] = gr[i]; }
+  } else
   if (l < 4) a.contact[b * 4 + l] = (a.p.foot_radius - S[SL_TIP + 6 * l + 2] > 0.0) ? 1 : 0;
   if (l < 12) a.force[(size_t)b * 12 + l] = (a.nsub > 0) ? fc[l] : 0.0;
   if (l == 0) { a.time[b] = time; a.ring_n[b * 2] = head; a.ring_n[b * 2 + 1] = cnt; a.status[b] = bad; }
   if constexpr (PUSH) { if (l < 9) pa.push_out[(size_t)b * 9 + l] = pw; if (l == 0) pa.push_mask[b] = pmask; }      // nsub == 0 (hand-over): nothing applied
 }
 
-__global__ void __launch_bounds__(64) qm_sim_kernel(QmSimArgs a) { sim_step_body<false>(a, QmPushArgs()); }
+__global__ void __launch_bounds__(64) qm_sim_kernel(QmSimArgs a) { sim_step_body<false, false>(a, QmPushArgs(), QmTerrainArgs()); }
 // the same step with the scheduled wrenches of QmPushArgs applied (one wavefront per instance, the same LDS carve)
-__global__ void __launch_bounds__(64) qm_sim_push_kernel(QmSimPushArgs a) { sim_step_body<true>(a.sim, a.push); }
+__global__ void __launch_bounds__(64) qm_sim_push_kernel(QmSimPushArgs a) { sim_step_body<true, false>(a.sim, a.push, QmTerrainArgs()); }
+// the same two steps on the ground of QmTerrainArgs (one wavefront per instance, the same LDS carve)
+__global__ void __launch_bounds__(64) qm_sim_terrain_kernel(QmSimTerrainArgs a) { sim_step_body<false, true>(a.sim, QmPushArgs(), a.ter); }
+__global__ void __launch_bounds__(64) qm_sim_terrain_push_kernel(QmSimTerrainPushArgs a) { sim_step_body<true, true>(a.sim, a.push, a.ter); }
+
+// the lookup at arbitrary points, one thread per point: out = {h, gx, gy, mu} with mu = mu_default where the terrain carries no friction grid
+struct QmTerrainEvalArgs { QmTerrainArgs ter; int B, n; double mu_default; const double* xy; double* out; };      // xy [B][n][2], out [B][n][4]
+__global__ void __launch_bounds__(64) qm_terrain_eval_kernel(QmTerrainEvalArgs a) {
+  const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (t >= (size_t)a.B * a.n) return;
+  const int b = (int)(t / a.n); const QmTerrainArgs& ta = a.ter; double* o = a.out + 4 * t;
+  if (b >= ta.nB) { o[0] = 0.0; o[1] = 0.0; o[2] = 0.0; o[3] = a.mu_default; return; }
+  const double* hdr = ta.hdr + (size_t)b * QM_TERRAIN_WORDS; const QmTerrainCell c = qm_terrain_cell(hdr, ta.nx, ta.ny, a.xy[2 * t], a.xy[2 * t + 1]);
+  const size_t base = (size_t)b * ta.ny * ta.nx; double h4[4], m4[4];
+  for (int k = 0; k < 4; ++k) { const size_t at = base + qm_terrain_corner(c, ta.nx, k); h4[k] = ta.height[at]; m4[k] = ta.mu ? ta.mu[at] : a.mu_default; }
+  o[0] = qm_terrain_blend(c, h4); qm_terrain_slope(c, hdr, h4, o[1], o[2]); o[3] = ta.mu ? qm_terrain_blend(c, m4) : a.mu_default;
+}

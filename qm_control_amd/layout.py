@@ -38,6 +38,8 @@ PLAN_RECORD_FIELDS = [("time", "<f8", 1, 8 * PT_TIME), ("mode", "<i4", 1, 8 * PT
 FOOTHOLD_FIELDS = [("time", "<f8", 1, 0), ("leg", "<i4", 1, 8), ("event", "<i4", 1, 12), ("pos", "<f8", 3, 16)]
 # struct qmhip_push (include/qmhip_layout.h): one scheduled external wrench on the plant
 PUSH_FIELDS = [("t_on", "<f8", 1, 0), ("t_off", "<f8", 1, 8), ("base_force", "<f8", 3, 16), ("base_torque", "<f8", 3, 40), ("ee_force", "<f8", 3, 64), ("spare", "<f8", 1, 88)]
+# struct qmhip_terrain (include/qmhip_layout.h): origin and spacing of one instance's ground grid (QM_TERRAIN_MAX, QM_TERRAIN_BYTES come from the header above)
+TERRAIN_FIELDS = [("x0", "<f8", 1, 0), ("y0", "<f8", 1, 8), ("dx", "<f8", 1, 16), ("dy", "<f8", 1, 24)]
 # struct qmhip_sensor (include/qmhip_layout.h): the sensor model of one instance of the plant
 SENSOR_FIELDS = [("seed", "<u8", 1, 0), ("lag", "<i4", 1, 8), ("spare0", "<i4", 1, 12), ("sigma", "<f8", 6, 16), ("bias_sigma", "<f8", 6, 64), ("spare", "<f8", 2, 112)]
 
